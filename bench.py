@@ -16,13 +16,19 @@ Workloads (--workload):
 One step = one pass of the hot path over the rank's share: every page of every selected column
 chunk decompressed and decoded into columnar buffers in HBM, compressed bytes already resident in
 HBM (device-resident). `value` = decoded bytes of all ranks / max-over-ranks step time.
-After the timed region (never inside it): bit-exact parity of the timed outputs against the CPU
-oracle, the dominant kernel's isolated launch time (roofline), the end-to-end rate (pinned host
-input -> H2D -> decode -> D2H into pinned host columns), and CPU baselines on the host cores.
-The dominant kernel's HBM traffic comes from rocprofv3 --pmc passes run as child processes
-before this process touches the GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sf1|sf100|wide]
+A plain run does only what that headline figure needs: it writes or finds the input, uploads it,
+warms up, times the K steps and prints the result line. --dump-outputs DIR also writes what the
+last timed step left in the streams' output arenas as DIR/<name>.npy (dump_outputs below).
+
+With --full, after the timed region (never inside it): bit-exact parity of the timed outputs
+against the CPU oracle, per-stage times, the dominant kernel's isolated launch time (roofline), the
+end-to-end rate (pinned host input -> H2D -> decode -> D2H into pinned host columns), the write
+path and CPU baselines on the host cores; the dominant kernel's HBM traffic comes from rocprofv3
+--pmc passes run as child processes before this process touches the GPU. Each of these legs has a
+--no-... switch that takes it out of a --full run.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sf1|sf100|wide] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself (child
@@ -553,6 +559,67 @@ def check_parity(path, pf, decs, last_batches, budget_threads):
             "mismatches": bad[:5], "against": "oracle/pf_oracle.c (CPU restatement, pinned to pyarrow golden vectors)"}
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+
+DUMP_BUDGET = 48 << 20   # payload bytes of all ranks' .npy files together (the limit is 64 MB)
+DUMP_SEED = 20240607     # the sampled positions depend on this, the array's place in the plan and its length only
+_VALUE_DTYPE = {1: np.int32, 2: np.int64, 4: np.float32, 5: np.float64}   # Parquet physical type -> numpy
+
+
+def _chunk_array_names(col):
+    """The arrays a caller receives for one decoded chunk of column `col` (GpuDecoder.fetch)."""
+    names = ["offsets", "chars"] if col.physical_type == 6 else ["values"]
+    if col.max_def > 0:
+        names.append("validity")
+    if col.max_rep == 1:
+        names += ["list_offsets", "list_validity"]
+    if col.max_rep > 0:
+        names += ["def_levels", "rep_levels"]
+    return names
+
+
+def sample_positions(stream, item, k, size, count):
+    """The `count` ascending positions at which array k of chunk `item` of stream `stream` is sampled."""
+    return np.sort(np.random.default_rng([DUMP_SEED, stream, item, k]).integers(0, size, count))
+
+
+def dump_outputs(out_dir, pf, decs, last_batches, rank=0, world=1):
+    """Every stream's last timed batch is still resident in its context's output arenas: copy each
+    chunk's arrays to the host as a caller would (GpuDecoder.fetch) and write them as
+    <out_dir>/[r<rank>_]s<stream>_i<item>_rg<row group>_c<column>_<array>.npy.
+    Numeric values, offsets and levels are written as float64 (float32 values, raw bytes and chars
+    as float32), validity bitmaps as one 0/1 float32 per slot. An array longer than its share of
+    DUMP_BUDGET is written as a sample at fixed, seeded, ascending positions. checksums.npy holds, per
+    written array in file-name order, [length, sum, sum of every 2nd, sum of every 3rd element] over the
+    WHOLE array (float64), so a sampled array is still covered end to end."""
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f"r{rank}_" if world > 1 else ""
+    n_arrays = sum(len(_chunk_array_names(pf.columns[c])) for bi in last_batches for (_p, c, *_r) in bi.items)
+    cap = max(1, DUMP_BUDGET // world // (8 * max(1, n_arrays) + 32))   # elements per array (8 B each at most)
+    sums = {}
+    for s, (dec, bi) in enumerate(zip(decs, last_batches)):
+        for i, (p, c, *_r) in enumerate(bi.items):
+            col = pf.columns[c]
+            g = dec.fetch(i, col.physical_type, col.max_def, col.max_rep)
+            if g["status"] != 0:
+                raise RuntimeError(f"--dump-outputs: stream {s} chunk {i} (rg {p}, column {c}) status {g['status']}")
+            for k, name in enumerate(_chunk_array_names(col)):
+                a = g[name]
+                if name == "values" and col.physical_type in _VALUE_DTYPE:
+                    a = a.view(_VALUE_DTYPE[col.physical_type])
+                elif name in ("validity", "list_validity"):
+                    a = np.unpackbits(a, bitorder="little")[:g["num_slots"] if name == "validity" else g["num_rows"]]
+                wide = a.dtype.itemsize > 1 and a.dtype != np.float32
+                key = f"{pre}s{s}_i{i}_rg{p}_c{c}_{name}"
+                with np.errstate(all="ignore"):   # a column holding infinities may sum to inf or NaN
+                    sums[key] = [float(a.size)] + [float(a[::st].sum(dtype=np.float64)) for st in (1, 2, 3)]
+                if a.size > cap:
+                    a = a[sample_positions(s, i, k, a.size, cap)]
+                np.save(os.path.join(out_dir, key + ".npy"), a.astype(np.float64 if wide else np.float32))
+    np.save(os.path.join(out_dir, f"{pre}checksums.npy"), np.array([sums[k] for k in sorted(sums)], dtype=np.float64).reshape(-1, 4))
+    return len(sums)
+
+
 # --------------------------------------------------------------------------- main
 
 def spawn_ranks(args, argv):
@@ -689,7 +756,7 @@ class ContextPool:
             t.join()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)   # ~1.2 s timed: long enough for an SMI sampler to see the GPU busy
@@ -718,11 +785,18 @@ def main():
     ap.add_argument("--columns", default=None, help=argparse.SUPPRESS)   # analysis only: comma-separated column subset
     ap.add_argument("--pool", type=int, default=100000,
                     help="wide: distinct values per column (SURVEY 8(d) sweep: 1K, 16K, 32K, 64K, 100K)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true")
-    ap.add_argument("--no-write", action="store_true", help="skip the write-path leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last step decoded as DIR/<name>.npy "
+                         "(float32 / float64, sampled at fixed positions where large; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity check against the oracle, the per-stage and "
+                         "roofline passes, the rocprofv3 --pmc traffic passes, the end-to-end and write legs and the "
+                         "CPU baselines (each can be taken out again with its --no-... switch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity check")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end leg")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 --pmc passes")
+    ap.add_argument("--no-write", action="store_true", help="--full without the write-path leg")
     ap.add_argument("--e2e-split", type=int, default=1, help="E2E: batches per row group (column subsets)")
     ap.add_argument("--e2e-streams", type=int, default=2,
                     help="E2E: decode streams (each with its twin context and the library's copy stream: the "
@@ -735,11 +809,18 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="timed steps decode -> wait per batch on one context per stream (A/B of the pipelined default)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    args, _ = ap.parse_known_args()
+    args, _ = ap.parse_known_args(argv)
     if args.string_weight is None:
         args.string_weight = WORKLOADS[args.workload].get("string_weight", 1.0)
     if args.slice_mult is None:
         args.slice_mult = WORKLOADS[args.workload].get("slice_mult", 1)
+    if not args.full:   # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_parity = args.no_e2e = args.no_pmc = args.no_write = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.pmc_child:
         return pmc_child(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -838,6 +919,12 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = float(tot[0]) * args.steps / dt / 1e9
 
+    # ---- --dump-outputs: the last timed step's arrays (each context's last batch is still resident) ----
+    if args.dump_outputs:
+        t1 = time.time()
+        n_dumped = dump_outputs(args.dump_outputs, pf, timed_last, [bl[-1] for bl in batches], rank, world)
+        log(f"[bench] wrote {n_dumped} arrays to {args.dump_outputs} in {time.time() - t1:.1f}s")
+
     # ---- parity of the timed outputs (each context's last batch is still resident) ----
     parity = None
     if not args.no_parity:
@@ -849,37 +936,50 @@ def main():
         log(f"[bench] parity {parity.get('chunks')} chunks bit_exact={parity.get('bit_exact')} in {time.time() - t1:.1f}s")
 
     # ---- per-stage times: separate untimed passes, all streams decoding, stage events on ----
-    pool.reset()
-    stage_passes = min(args.steps, 10)
-    pool.run(stage_passes, pipelined=False)
-    stage_ms = {k: v / (stage_passes * n_b0) for k, v in pool.stage_acc.items()}
+    stage_ms, roofline, achieved, traffic_detail = None, None, None, None
+    if args.full:
+        pool.reset()
+        stage_passes = min(args.steps, 10)
+        pool.run(stage_passes, pipelined=False)
+        stage_ms = {k: v / (stage_passes * n_b0) for k, v in pool.stage_acc.items()}
 
-    # ---- roofline of the dominant stage: context 0's first batch decoded alone ----
-    b0 = batches[0][0]
-    st0 = page_stats(b0.descs, [pf.columns[c] for (_p, c, *_r) in b0.items])
-    dbytes0 = 0
-    iso = {}
-    dec = decs[0]
-    for r in range(ROOF_PASSES):
-        dec.decode(b0.descs, b0.dev.value, b0.nbytes, on_device=True)
-        if dec.wait() != 0 and not _SKIP:
-            raise RuntimeError(dec.error())
-        for k, v in dec.timing().items():
-            iso[k] = iso.get(k, 0.0) + v / ROOF_PASSES
-    for i, (p, c, *_r) in enumerate(b0.items):
-        dbytes0 += chunk_decoded_bytes(pf.columns[c], dec.info(i))
-    kern_bytes = stage_bytes(st0, dbytes0)
-    dom = max((k for k in iso if k in kern_bytes), key=lambda k: iso.get(k, 0.0))
-    dom_ms = iso.get(dom, 0.0)
-    dom_bytes = kern_bytes[dom]
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else None
-    traffic, traffic_detail, traffic_names = None, None, None
-    if pmc and "error" not in pmc:
-        traffic_detail = pmc_traffic_per_kernel(pmc)
-        names = [n for n in traffic_detail if STAGE_KERNELS.get(dom) and re.match(STAGE_KERNELS[dom], n.split("<")[0])]
-        if names:
-            traffic = sum(traffic_detail[n]["traffic_bytes"] for n in names)
-            traffic_names = sorted(names)
+        # ---- roofline of the dominant stage: context 0's first batch decoded alone ----
+        b0 = batches[0][0]
+        st0 = page_stats(b0.descs, [pf.columns[c] for (_p, c, *_r) in b0.items])
+        dbytes0 = 0
+        iso = {}
+        dec = decs[0]
+        for r in range(ROOF_PASSES):
+            dec.decode(b0.descs, b0.dev.value, b0.nbytes, on_device=True)
+            if dec.wait() != 0 and not _SKIP:
+                raise RuntimeError(dec.error())
+            for k, v in dec.timing().items():
+                iso[k] = iso.get(k, 0.0) + v / ROOF_PASSES
+        for i, (p, c, *_r) in enumerate(b0.items):
+            dbytes0 += chunk_decoded_bytes(pf.columns[c], dec.info(i))
+        kern_bytes = stage_bytes(st0, dbytes0)
+        dom = max((k for k in iso if k in kern_bytes), key=lambda k: iso.get(k, 0.0))
+        dom_ms = iso.get(dom, 0.0)
+        dom_bytes = kern_bytes[dom]
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else None
+        traffic, traffic_names = None, None
+        if pmc and "error" not in pmc:
+            traffic_detail = pmc_traffic_per_kernel(pmc)
+            names = [n for n in traffic_detail if STAGE_KERNELS.get(dom) and re.match(STAGE_KERNELS[dom], n.split("<")[0])]
+            if names:
+                traffic = sum(traffic_detail[n]["traffic_bytes"] for n in names)
+                traffic_names = sorted(names)
+        roofline = {"bound": "hbm", "kernel": STAGE_LABEL.get(dom, dom), "achieved": round(achieved, 2) if achieved else None,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None, "traffic": traffic,
+                    "traffic_source": "rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch, measured in "
+                                      "this run (child processes, same batch, 1 stream)" if traffic else
+                                      (pmc or {}).get("error"),
+                    "algorithmic_bytes_per_launch": dom_bytes, "algorithmic_bytes_def": STAGE_BYTES_DEF.get(dom),
+                    "traffic_kernels": traffic_names, "launch_ms": round(dom_ms, 4),
+                    "launch_ms_source": f"HIP events on context 0's stream, its first batch decoded alone x{ROOF_PASSES} "
+                                        "after the timed region",
+                    "stage_ms_overlapped": round(stage_ms.get(dom, 0.0), 4)}
     b_alg_step = None
     descs_all = [d for bl in batches for bi in bl for d in bi.descs]
     st_all = page_stats(descs_all)
@@ -980,26 +1080,21 @@ def main():
                                    + (f", BYTE_ARRAY chunks weighted x{args.string_weight:g}" if args.string_weight != 1.0 else "")
                                    + (f", x{args.slice_mult} row-group slices per column" if args.slice_mult != 1 else "")
                                    + ")" if args.split == "columns" and S > 1 and wl_batch(args) <= 0 else "")},
-        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()} if args.full else None,
         "stage_ms_source": "context 0's per-stage HIP events, separate untimed passes (all streams decoding, "
                            "not pipelined); the timed steps run with the events off",
         "pipelined": not args.no_pipeline,
         "host_enqueue_ms_per_batch": round(host_plan_ms, 4),
-        "roofline": {"bound": "hbm", "kernel": STAGE_LABEL.get(dom, dom), "achieved": round(achieved, 2) if achieved else None,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None, "traffic": traffic,
-                     "traffic_source": "rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch, measured in "
-                                       "this run (child processes, same batch, 1 stream)" if traffic else
-                                       (pmc or {}).get("error"),
-                     "algorithmic_bytes_per_launch": dom_bytes, "algorithmic_bytes_def": STAGE_BYTES_DEF.get(dom),
-                     "traffic_kernels": traffic_names, "launch_ms": round(dom_ms, 4),
-                     "launch_ms_source": f"HIP events on context 0's stream, its first batch decoded alone x{ROOF_PASSES} "
-                                         "after the timed region",
-                     "stage_ms_overlapped": round(stage_ms.get(dom, 0.0), 4)},
+        "roofline": roofline,
         "pipeline_roofline": {"b_alg_per_step_rank0": b_alg_step, "ms_per_step": round(ms_per_step, 4),
                               "achieved": round(b_alg_step / (ms_per_step * 1e-3) / 1e9, 2),
                               "frac": step_frac},
     }
+    if not args.full:   # measured by passes of their own, which a plain run does not make
+        for k in ("dominant_kernel_frac", "stage_ms", "stage_ms_source", "roofline"):
+            del out[k]
+    if args.dump_outputs:
+        out["dump_outputs"] = args.dump_outputs
     if traffic_detail:
         out["pmc_traffic_per_launch"] = traffic_detail
     if parity is not None:

@@ -9,6 +9,6 @@ SETS=$1; shift
 mkdir -p "$OUT"
 for c in $SETS; do
   f="$OUT/c_${c//,/_}.json"
-  timeout -k 10 200 python -u bench.py --columns $c --steps 50 --warmup 5 --no-cpu-baseline --no-pmc --no-e2e --no-write --no-parity "$@" > "$f" 2>> "$OUT/err.log" || { tail -20 "$OUT/err.log"; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --columns $c --steps 50 --warmup 5 --no-cpu-baseline --no-pmc --no-e2e --no-write --no-parity "$@" > "$f" 2>> "$OUT/err.log" || { tail -20 "$OUT/err.log"; exit 1; }
   python -c "import json; d=json.load(open('$f')); print('$c', d['ms_per_step'], d['value'], {k: round(v,3) for k,v in d['stage_ms'].items() if v > 0.02})"
 done

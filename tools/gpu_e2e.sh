@@ -8,7 +8,7 @@ cd "$ROOT" || exit 1
 OUT="$ROOT/gpurun_out/${1:-e2e}"; mkdir -p "$OUT"
 timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -k "batch_copy or multi_device" -m gpu -x -q --timeout 120 --timeout-method thread > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 1; }
 tail -1 "$OUT/pytest.log"
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-pmc --no-write --no-parity"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --no-write --no-parity"
 DIAG=$ROOT/parquet-floor_amd/diag/libpfloor_diag.so
 one() {   # name, extra bench args (env via ENV=...)
   local name=$1; shift

@@ -6,7 +6,7 @@ set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$ROOT" || exit 1
 OUT="$ROOT/gpurun_out/${1:-e2eh2d}"; shift; mkdir -p "$OUT"
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-pmc --no-write --no-parity"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --no-write --no-parity"
 for i in 1 2; do
   for g in base "$@"; do
     if [ "$g" == base ]; then

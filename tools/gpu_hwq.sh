@@ -4,7 +4,7 @@ set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$ROOT" || exit 1
 OUT="$ROOT/gpurun_out/${1:-hwq}"; mkdir -p "$OUT"
-B="--steps 150 --warmup 5 --no-cpu-baseline --no-pmc --no-e2e --no-write"
+B="--full --steps 150 --warmup 5 --no-cpu-baseline --no-pmc --no-e2e --no-write"
 for i in 1 2; do
   for cfg in "4 4" "8 4" "8 5" "8 6" "8 8" "4 4"; do
     set -- $cfg

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 pass() {
     local name="$1"; shift
     timeout -s KILL 240 rocprofv3 --pmc "$@" --kernel-include-regex "$KRE" --output-format csv -d "$OUT/$name" -o run -- \
-        python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-e2e --no-parity --streams 1 $BENCH_ARGS \
+        python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-e2e --no-parity --streams 1 $BENCH_ARGS \
         > "$OUT/$name.log" 2>&1
 }
 BENCH_ARGS="$*"
