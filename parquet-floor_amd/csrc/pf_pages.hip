@@ -2236,6 +2236,9 @@ __global__ __launch_bounds__(64) void k_snappy_head(SnappyJob* __restrict__ jobs
     // PLAIN fixed width, flat, all present
     const int w = ck.width;
     if (pg.encoding != 0 || ck.max_rep != 0 || ck.ptype == 0 || ck.ptype == 6 || w <= 0 || !ck.values) return;
+    // a page with a level table (null count not known to be zero: a v1 page without statistics) is decoded
+    // from its scratch body by k_page_null / k_lvl + k_flat_null, which would overwrite values written direct
+    if (pg.lvltab != nullptr) return;
     const uint32_t ne = uint32_t(pg.num_values);
     uint32_t L = 0;
     if (ck.max_def > 0) {

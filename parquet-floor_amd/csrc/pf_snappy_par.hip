@@ -1531,6 +1531,9 @@ enum : uint32_t { R5_NORMAL = 0, R5_LONG = 1, R5_NOP = 2, R5_END = 3, R5_BAD = 4
 // x - offset * (1 + floor(j / offset)), the byte an overlapping copy reads as j mod offset. Entry 0 is a
 // dummy literal for the batch's alignment bytes (token t of the batch is entry t + 1).
 constexpr uint32_t X5_CP = 0x80000000u;
+// A ring copy's offset is at most XRING - 1 (near: off <= (otok - op) + XRING - X5_BATCH); the (j * m) >> 16
+// identity is checked for offsets below 4096 (tests/test_exec_arith.py) and PF_XRING is a build-time override.
+static_assert(XRING <= 4096u, "ring-copy offsets must stay below 4096: tests/test_exec_arith.py checks (j * m) >> 16 up to there");
 
 // Workgroup barrier for LDS hand-over only (no wait on outstanding global stores).
 __device__ __forceinline__ void x5_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -1,6 +1,9 @@
 """K1 (Snappy) on the GPU in isolation: known-answer vectors (pyarrow's Google Snappy), seeded
 multi-block streams from the oracle's test compressor (Google-style 64 KiB blocks -> the
-block-parallel path; cross-block streams -> the whole-page re-run), and corrupt streams.
+block-parallel path; cross-block streams -> the whole-page re-run). Every stream here comes out of a
+compressor; hand-assembled streams (token by token, including tokens no compressor of the suite emits)
+and corrupt raw streams are in test_gpu_snappy_tokens.py, hand-built Snappy pages in
+test_gpu_snappy_pages.py (CPU half: test_snappy_tokens.py).
 pf_snappy_last_fallback: 0 block-parallel, 1 whole page in one executor wave, 2 pieces re-run as
 one (block assumption broken), 3 serial kernel (stream not indexable / corrupt)."""
 import os
