@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pf_device.h"
+#include "pf_launch.h"
 
 namespace pf {
 

@@ -22,6 +22,27 @@ enum : int32_t {
     ST_OK = 0, ST_CORRUPT = -2, ST_ENCODING = -3, ST_CODEC = -4, ST_CAPACITY = -6, ST_TYPE = -7
 };
 
+// Window hand-overs (WinPub, pf_internal.h)
+__device__ __forceinline__ void winpub_put(WinPub& me, uint64_t p, uint64_t e, uint32_t st) {
+    // st + 1 in the low two bits (never 0); a position or count past 31 bits publishes 3 (overflow)
+    const bool ovf = p > 0x7fffffffull || e > 0x7fffffffull || st > 1u;
+    const uint64_t w = (uint64_t(p & 0x7fffffffu) << 33) | (uint64_t(e & 0x7fffffffu) << 2) | uint64_t(ovf ? 3u : st + 1u);
+    __hip_atomic_store(&me.w, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Waits up to spin_cap polls; false: no hand-over came (or it overflowed), the caller gives the page up.
+__device__ __forceinline__ bool winpub_get(const WinPub& pv, uint32_t spin_cap, uint64_t& p, uint64_t& e, uint32_t& st) {
+    if (spin_cap == 0) return false;   // (diagnostics: every hand-over times out)
+    uint64_t w;
+    uint32_t spins = 0;
+    while ((w = __hip_atomic_load(&pv.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && ++spins < spin_cap)
+        __builtin_amdgcn_s_sleep(2);
+    if (w == 0 || (w & 3u) == 3u) return false;
+    p = w >> 33;
+    e = (w >> 2) & 0x7fffffffull;
+    st = uint32_t(w & 3u) - 1u;
+    return true;
+}
+
 __device__ __forceinline__ void set_status(DevChunkResult* res, int chunk, int32_t code, int page) {
     // the most negative code wins; any error is sticky
     int32_t prev = atomicMin(&res[chunk].status, code);

@@ -1,5 +1,5 @@
-// pf_internal.h — device-side work descriptors shared by the HIP kernels and the host
-// runtime (pf_runtime.hip). Not part of the C ABI.
+// pf_internal.h — device-side work descriptors shared by the HIP kernels, the host planner
+// (pf_plan.cpp) and the host runtime (pf_runtime.hip). Not part of the C ABI.
 //
 // HBM layout of one decode batch (one pf_decode_row_group call):
 //   in      : the caller's chunk bytes (resident, or one H2D copy of the pinned buffer)
@@ -11,7 +11,20 @@
 #pragma once
 #include <stdint.h>
 
+// The host planner (pf_plan.cpp) includes this header from plain C++
+#ifdef __HIPCC__
+#define PF_HD __host__ __device__
+#else
+#define PF_HD
+#endif
+
 namespace pf {
+
+// (a, b) index pair of the launch tables: (job, window), (job, piece), (job, tile), (page, block),
+// (page, segment). Laid out as HIP's int2, which is how the kernels read it.
+struct Int2 {
+    int x, y;
+};
 
 // Decoder options. The product library (libpfloor.so) always runs these defaults and reads no
 // environment. The diagnostics build (-DPF_DIAG, diag/libpfloor_diag.so) takes them from PF_*
@@ -21,16 +34,13 @@ struct PfOpts {
     int exec = 5;             // PF_EXEC: block-parallel Snappy executor: 5 producer / consumer | 2 one wave
     bool ba_fused = true;     // PF_BA_FUSED=0: the round-3 PLAIN BYTE_ARRAY walk kernels
     bool page_null = false;   // PF_PAGE_NULL=1: k_page_null before k_lvl
-    bool null_dict_lds = true;   // PF_NULL_DICT_LDS=0: k_flat_null never stages its dictionary
     int null_stagger = 0;     // PF_DEBUG_NULL_STAGGER=k: k_flat_null's blocks > 0 wait k rounds (race tests)
     bool nest_timeout = false;   // PF_DEBUG_NEST_TIMEOUT=1: every k_nest_lvl hand-over times out (whole-page path; tests)
     uint32_t null_dcap = 0;   // PF_NULL_DCAP=b: k_flat_null's level-byte stage instead of the batch's (16: blocks with
                               // level bytes do not fit, so k_lvl refuses the page and the fallback queue decodes it; tests)
-    bool piece_order = true;  // PF_PIECE_ORDER=0: Snappy pieces in page order
     unsigned debug_skip = 0;  // PF_DEBUG_SKIP=parse,exec,ba,levels,count,flat,decode (results are wrong)
     int force_serial = 0;     // PF_DEBUG_FORCE_SERIAL=k: every k-th Snappy job to the serial kernel
     int force_redo = 0;       // PF_DEBUG_FORCE_REDO=k: every k-th Snappy job rejected by the block executor
-    bool exec_stream = false; // PF_EXEC_STREAM=1: the executor on a low-priority stream of its own
     bool zc = true;           // PF_ZC=0: SDMA copies for the batch tables instead of k_copy_words
     bool dl_kernel = true;    // PF_DL_KERNEL=0: pf_copy_batch_async by SDMA copies instead of k_download
     bool h2d_kernel = false;  // PF_H2D_KERNEL=1: pinned chunk bytes to the device by a kernel instead of SDMA (E2E: no gain, r06)
@@ -42,8 +52,33 @@ struct PfOpts {
     bool nest_seg_set = false;
     bool dbp_par = true;      // PF_DBP_PAR=0: every DELTA_BINARY_PACKED page on k_delta
     int fix_shift = 1;        // PF_FIX_BLK=4096|8192|16384: fixed-width flat blocks (log2 of the multiple of 4096)
-    int decode_grid = 32;     // PF_DECODE_GRID: k_decode blocks when no page is known to need it (grid-stride check)
-    int count_grid = 64;      // PF_COUNT_GRID: k_count blocks (grid-stride; nearly every page is counted by k_count_flat)
+};
+
+// Numbers the host planner sizes tables by and the kernels index them by
+constexpr uint32_t FBLK = 4096;            // entries per (page, block) pair of the flat kernels
+constexpr uint32_t BA_TILE = 8192;         // stream bytes per PLAIN BYTE_ARRAY walk tile (k_ba_*)
+// k_ba_tile links values of up to ~124 bytes within a tile; pages of longer values would all take
+// the exact fallback walk there, so a batch with a walk whose values average more than BA_SHORT
+// bytes keeps the multi-kernel walk
+constexpr uint64_t BA_SHORT = 48;
+constexpr uint32_t STICKY_DICT = 64u << 10;   // dictionaries above this keep their chunk's flat blocks on one XCD label
+constexpr uint32_t SNAP_RB = 128;                 // input bytes per lane region (Snappy index pass)
+constexpr uint32_t SNAP_WIN = 64 * SNAP_RB;       // 8 KiB of input per index window
+constexpr uint32_t SNAP_WWORDS = SNAP_WIN / 32;   // token-start bitmap words per window
+constexpr uint32_t SNAP_BLOCK = 65536;            // Google Snappy block = executor piece
+
+// Result of the Snappy index pass for one 8 KiB input window.
+struct SnapWin {
+    uint32_t entry;   // chain start the window's bitmap was built from
+    uint32_t exit;    // first chain position at/after the window end (or the stream end)
+    uint32_t out;     // output bytes of the tokens in the window (on that chain)
+    uint32_t flags;
+};
+
+// Snappy entry-table record (pos carries a 2-bit flag in its top bits).
+struct SnapEnt {
+    uint32_t pos;
+    uint32_t out;
 };
 
 enum : int32_t {
@@ -156,30 +191,10 @@ struct DevPage {
 // whether the chain ended (st = 1) -- packed in one 64-bit word (0 until published) that is stored and
 // polled with relaxed agent-scope atomics (round 5: three stores and a release flag made every
 // hand-over write back the XCD's L2 and every acquire invalidate the reader's).
+// winpub_put / winpub_get: pf_device.h.
 struct WinPub {
     uint64_t w;
 };
-#ifdef __HIPCC__
-__device__ __forceinline__ void winpub_put(WinPub& me, uint64_t p, uint64_t e, uint32_t st) {
-    // st + 1 in the low two bits (never 0); a position or count past 31 bits publishes 3 (overflow)
-    const bool ovf = p > 0x7fffffffull || e > 0x7fffffffull || st > 1u;
-    const uint64_t w = (uint64_t(p & 0x7fffffffu) << 33) | (uint64_t(e & 0x7fffffffu) << 2) | uint64_t(ovf ? 3u : st + 1u);
-    __hip_atomic_store(&me.w, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// Waits up to spin_cap polls; false: no hand-over came (or it overflowed), the caller gives the page up.
-__device__ __forceinline__ bool winpub_get(const WinPub& pv, uint32_t spin_cap, uint64_t& p, uint64_t& e, uint32_t& st) {
-    if (spin_cap == 0) return false;   // (diagnostics: every hand-over times out)
-    uint64_t w;
-    uint32_t spins = 0;
-    while ((w = __hip_atomic_load(&pv.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && ++spins < spin_cap)
-        __builtin_amdgcn_s_sleep(2);
-    if (w == 0 || (w & 3u) == 3u) return false;
-    p = w >> 33;
-    e = (w >> 2) & 0x7fffffffull;
-    st = uint32_t(w & 3u) - 1u;
-    return true;
-}
-#endif
 #ifndef PF_NEST_WIN
 #define PF_NEST_WIN 2048
 #endif
@@ -201,7 +216,7 @@ struct SegRec {
 constexpr uint32_t NEST_CK_BYTES = 40;      // sizeof(RleState) (pf_device.h)
 constexpr uint32_t NEST_SEG = 2048;         // default entries per segment
 constexpr uint32_t NEST_MAX_SEGS = 1024;    // segments per page (k_nest_scan keeps their targets in LDS)
-__host__ __device__ inline uint64_t nest_seg_bytes(int32_t nseg) {
+PF_HD inline uint64_t nest_seg_bytes(int32_t nseg) {
     return uint64_t(nseg) * (3ull * NEST_CK_BYTES + sizeof(SegRec));
 }
 
@@ -227,7 +242,7 @@ constexpr uint32_t NL_SLACK = 256;         // run-header bytes a block's level /
 struct NullCaps {
     uint32_t dcap, icap, dlds;
 };
-__host__ __device__ inline uint32_t lvl_table_cap(int32_t num_values) {
+PF_HD inline uint32_t lvl_table_cap(int32_t num_values) {
     // RLE runs are >= 8 repeats and bit-packed groups 8 values for the writers we know (parquet-mr,
     // Arrow): <= 2 runs per 16 entries; a page needing more is left to k_flat / k_decode
     return uint32_t(num_values) / 8u + 64u;

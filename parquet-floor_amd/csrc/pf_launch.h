@@ -1,0 +1,56 @@
+// pf_launch.h — the kernel launchers the runtime (pf_runtime.hip) calls. Included by every file
+// that defines one, so a definition that drifts from its prototype does not compile.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "pf_internal.h"
+#include "pfloor.h"
+
+namespace pf {
+
+// pf_snappy.hip, pf_snappy_par.hip
+void launch_snappy_serial(const SnappyJob* d_jobs, int n_jobs, const int* d_fallback, DevChunkResult* d_res, hipStream_t s);
+void launch_snappy_parse(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int n_wins, SnapWin* d_win, SnapEnt* d_ent,
+                         uint32_t* d_lane_out, uint32_t* d_splits, int* d_fb, int max_nwin, hipStream_t s);
+void launch_snappy_exec(const SnappyJob* d_jobs, int n_jobs, const int2* d_pieces, int n_pieces, uint32_t* d_splits, int* d_fb,
+                        DevChunkResult* d_res, int exec, hipStream_t s);
+void launch_snappy(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int n_wins, SnapWin* d_win, SnapEnt* d_ent,
+                   uint32_t* d_lane_out, const int2* d_pieces, int n_pieces, uint32_t* d_splits, int* d_fb,
+                   DevChunkResult* d_res, int max_nwin, int exec, hipStream_t s);
+
+// pf_pages.hip
+void launch_snappy_head(SnappyJob* d_jobs, int n_jobs, DevPage* d_pages, const DevChunk* d_chunks, int* d_fb,
+                        const DevChunkResult* d_res, hipStream_t st);
+void launch_snappy_litcopy(const SnappyJob* d_jobs, const int* d_list, int n, const int* d_fb, hipStream_t st);
+void launch_ba(BaJob* d_jobs, int n_jobs, const int2* d_tiles, int n_tiles, DevChunkResult* d_res, hipStream_t st,
+               bool short_values);
+void launch_runs(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
+void launch_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st,
+                bool page_null, NullCaps nc);
+void launch_nest_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int max_nwin, DevChunkResult* d_res,
+                     hipStream_t st, bool force_timeout);
+void launch_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_flat, const int2* d_dblk,
+                  int n_dblk, DevChunkResult* d_res, BaJob* d_bajobs, hipStream_t st, int idle_grid);
+void launch_nest_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, const int2* d_segs, int n_segs,
+                       DevChunkResult* d_res, hipStream_t st);
+void launch_scan(DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, uint8_t* arena,
+                 uint64_t cap, unsigned long long* used, hipStream_t st);
+void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
+                 DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
+void launch_decode(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_first, DevChunkResult* d_res,
+                   hipStream_t st, int idle_grid);
+void launch_nest_decode(const DevChunk* d_chunks, DevPage* d_pages, const int2* d_segs, int n_segs, DevChunkResult* d_res,
+                        hipStream_t st);
+
+// pf_delta.hip
+void launch_delta(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int max_dbp_nwin, DevChunkResult* d_res,
+                  hipStream_t st);
+void launch_dlen(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
+void launch_dba_chars(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
+
+// pf_scan.hip
+void launch_page_scan(const ScanChunk* d_chunks, int n_chunks, pf_page_desc* d_pages, ScanCrc* d_crcs, ScanResult* d_res,
+                      hipStream_t s);
+void launch_page_crc(const ScanCrc* d_crcs, const int* d_list, int n, ScanResult* d_res, int32_t* d_bad, hipStream_t s);
+
+}  // namespace pf

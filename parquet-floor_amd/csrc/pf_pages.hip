@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pf_device.h"
+#include "pf_launch.h"
 #include "pf_snappy_par.h"
 
 namespace pf {
@@ -399,7 +400,7 @@ __device__ inline int64_t binary_walk_wg(const uint8_t* p, uint64_t n, int64_t c
 //   k_ba_verify every accepted value's end must be the next accepted value's start, value 0 at 0;
 //   k_ba_fallback  jobs that failed any check take the workgroup walk (binary_walk_wg, which ends
 //               in the exact serial walk), so results never depend on the filters.
-constexpr uint32_t BA_TILE = NT * 32;          // 8 KiB of stream per tile: one bitmap word per thread
+static_assert(BA_TILE == NT * 32, "8 KiB of stream per tile (pf_internal.h): one bitmap word per thread");
 constexpr uint32_t BA_STAGE = BA_TILE + 32;    // + alignment shift and the lookahead of a length
 
 __device__ __forceinline__ uint32_t ba_stage(uint8_t* stg, const uint8_t* p, uint64_t n, uint64_t base) {
@@ -883,7 +884,7 @@ __global__ __launch_bounds__(NT) void k_ba_fallback(BaJob* __restrict__ jobs, in
 
 // ---- values helpers ------------------------------------------------------------------------
 constexpr uint32_t DSTR_CAP = 256;   // string dictionaries up to this many entries: {pos, len} staged in LDS
-constexpr uint32_t FBLK = 4096;      // entries per k_flat workgroup: pages are split into blocks
+// FBLK (pf_internal.h): entries per k_flat workgroup: pages are split into blocks
 
 // BYTE_ARRAY data pages: chars of the entries before each FBLK block (k_count, dictionary pages),
 // kept after the page's aux entries.

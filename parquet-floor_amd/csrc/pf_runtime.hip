@@ -1,9 +1,10 @@
-// pf_runtime.hip — context, batch planning and kernel orchestration behind include/pfloor.h.
+// pf_runtime.hip — context, arenas and kernel orchestration behind include/pfloor.h.
 //
 // One pf_ctx per GPU (one HIP stream, growable HBM arenas, pinned staging). A decode batch is
-// any set of column chunks (a row group's selected columns, or several row groups): the host
-// turns the descriptors into flat DevChunk / DevPage / SnappyJob tables, uploads them in one
-// copy, and enqueues
+// any set of column chunks (a row group's selected columns, or several row groups). The host
+// planner (pf_plan.cpp, no HIP calls) turns the descriptors into flat DevChunk / DevPage /
+// SnappyJob tables, launch lists and arena sizes; this file grows the arenas to those sizes, has
+// the planner bind its offsets to them, uploads the tables in one copy, and enqueues
 //   k_snappy -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
 // on the context stream. Nothing synchronises until pf_wait.
 #include <hip/hip_runtime.h>
@@ -20,35 +21,14 @@
 
 #include "pf_encode.h"
 #include "pf_host.h"
+#include "pf_launch.h"
+#include "pf_plan.h"
 #include "pf_snappy_par.h"
 #include "pfloor.h"
 
-namespace pf {
-void launch_snappy(const SnappyJob*, int, const int2*, int, SnapWin*, SnapEnt*, uint32_t*, const int2*, int, uint32_t*,
-                   int*, DevChunkResult*, int, int, hipStream_t);
-void launch_snappy_parse(const SnappyJob*, int, const int2*, int, SnapWin*, SnapEnt*, uint32_t*, uint32_t*, int*, int,
-                         hipStream_t);
-void launch_snappy_exec(const SnappyJob*, int, const int2*, int, uint32_t*, int*, DevChunkResult*, int, hipStream_t);
-void launch_ba(BaJob*, int, const int2*, int, DevChunkResult*, hipStream_t, bool);
-void launch_snappy_head(SnappyJob*, int, DevPage*, const DevChunk*, int*, const DevChunkResult*, hipStream_t);
-void launch_snappy_litcopy(const SnappyJob*, const int*, int, const int*, hipStream_t);
-void launch_delta(const DevChunk*, DevPage*, const int*, int, int, DevChunkResult*, hipStream_t);
-void launch_dlen(const DevChunk*, DevPage*, const int*, int, DevChunkResult*, hipStream_t);
-void launch_dba_chars(const DevChunk*, DevPage*, const int*, int, DevChunkResult*, hipStream_t);
-void launch_count(const DevChunk*, DevPage*, const int*, int, int, const int2*, int, DevChunkResult*, BaJob*, hipStream_t, int);
-void launch_scan(DevChunk*, DevPage*, const int*, int, DevChunkResult*, uint8_t*, uint64_t, unsigned long long*, hipStream_t);
-void launch_flat(const DevChunk*, DevPage*, const int*, int, int, int, int, int*, DevChunkResult*, hipStream_t, NullCaps, int);
-void launch_lvl(const DevChunk*, DevPage*, const int*, int, DevChunkResult*, hipStream_t, bool, NullCaps);
-void launch_runs(const DevChunk*, DevPage*, const int*, int, DevChunkResult*, hipStream_t);
-void launch_decode(const DevChunk*, DevPage*, const int*, int, int, DevChunkResult*, hipStream_t, int);
-void launch_nest_lvl(const DevChunk*, DevPage*, const int*, int, int, DevChunkResult*, hipStream_t, bool);
-void launch_nest_count(const DevChunk*, DevPage*, const int*, int, const int2*, int, DevChunkResult*, hipStream_t);
-void launch_nest_decode(const DevChunk*, DevPage*, const int2*, int, DevChunkResult*, hipStream_t);
-void launch_page_scan(const ScanChunk*, int, pf_page_desc*, ScanCrc*, ScanResult*, hipStream_t);
-void launch_page_crc(const ScanCrc*, const int*, int, ScanResult*, int32_t*, hipStream_t);
-}  // namespace pf
-
 using namespace pf;
+
+static_assert(sizeof(Int2) == sizeof(int2) && alignof(Int2) <= alignof(int2), "the planner's pairs are the kernels' int2");
 
 namespace {
 
@@ -124,8 +104,6 @@ inline void copy_words(void* d0, const void* s0, size_t b0, void* d1, const void
                        static_cast<uint64_t*>(d1), static_cast<const uint64_t*>(s1), n1);
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // A decoded batch into pinned host memory by a kernel writing through the pages' device address
 // (round 6): the SDMA engines move one direction at a time on this link -- an SDMA H2D and an SDMA D2H
 // together make 57 GB/s, an SDMA H2D beside this kernel's D2H 86 GB/s (profiles/r06_e2e/duplex.txt) --
@@ -153,17 +131,14 @@ __global__ __launch_bounds__(256) void k_download(DlRange r0, DlRange r1, DlRang
 }
 
 constexpr int N_EVENTS = 11;  // h2d, snappy parse, snappy exec, dict, delta, levels, count, scan, flat, decode
-constexpr uint32_t BA_TILE_BYTES = 8192;   // pf_pages.hip BA_TILE
-constexpr int64_t FLAT_BLK = 4096;         // pf_pages.hip FBLK   // h2d, snappy, dict, delta, count, scan, flat, decode
 
 }  // namespace
 
-// The HIP stream(s) of a context. Shared by contexts made with pf_ctx_create_shared (the stream
+// The HIP streams of a context. Shared by contexts made with pf_ctx_create_shared (the stream
 // lives until the last of them is destroyed).
 struct Streams {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t exec_stream = nullptr;
     // pf_copy_batch_async's downloads (made on first use): the next batch's H2D and kernels on `stream`
     // (a twin context's, with its own arenas) run while this batch's columns go to the host
     hipStream_t copy_stream = nullptr;
@@ -171,7 +146,6 @@ struct Streams {
     ~Streams() {
         (void)hipSetDevice(device);
         if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-        if (exec_stream) { (void)hipStreamSynchronize(exec_stream); (void)hipStreamDestroy(exec_stream); }
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     }
 };
@@ -181,11 +155,6 @@ struct pf_ctx {
     pf::PfOpts opts;                       // defaults; the diagnostics build reads PF_* at creation
     std::shared_ptr<Streams> streams;
     hipStream_t stream = nullptr;          // = streams->stream
-    // PF_EXEC_STREAM=1: the Snappy executor runs on a low-priority stream of its own (event-ordered
-    // with `stream`, which then gets the high priority), so the short kernels of another context
-    // get CUs ahead of this context's executor waves as those retire.
-    hipStream_t exec_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool zc = true;                        // metadata / results copied by k_copy_words (PF_ZC=0: SDMA copies)
     hipEvent_t ev[N_EVENTS] = {};
     // recorded after the last operation of this context's decode: pf_wait waits for it, not for the
@@ -209,39 +178,14 @@ struct pf_ctx {
     bool copies_pending = false;           // pf_copy_columns_async enqueued, not yet pf_sync'ed
     bool tables_from_decode = false;       // d_meta layout (off_fallback) belongs to a pf_decode_row_group
     bool timing_valid = false;
-    std::vector<DevChunk> chunks;          // host copies (device pointers)
-    std::vector<DevPage> pages;
-    std::vector<SnappyJob> jobs;
-    std::vector<int> l_dictbin, l_delta, l_count, l_scan, l_flat, l_decode, l_runs, l_dlen, l_dba, l_lvl, l_djobs, l_nest, l_nseg,
-        l_cdict;   // l_cdict: (page, block) pairs of flat dictionary BYTE_ARRAY pages (k_count_dict)
-    std::vector<int2> wins, pieces;       // Snappy index windows / 64 KiB pieces (job, index)
-    std::vector<BaJob> bajobs;             // PLAIN BYTE_ARRAY walks: dictionary pages, then data pages
-    std::vector<int2> ba_tiles;            // (job relative to its batch, tile)
-    int n_ba_dict = 0, n_ba_dict_tiles = 0;
-    bool ba_short_dict = true, ba_short_data = true;   // every walk job's values average <= BA_SHORT bytes: k_ba_tile
-    uint32_t null_dict_lds = 0;            // bytes of the largest nullable-page dictionary that fits k_flat_null's LDS stage
-    bool meta_by_kernel = false;   // this batch's metadata went up by k_upload (which also zeroes bits / npub)
-    uint32_t null_dcap = 16, null_icap = 16;   // k_flat_null's level / id byte stages (NullCaps)
-    int max_snap_win = 1;                  // index windows of the batch's largest Snappy job (k_snappy_chain's tables)
-    uint32_t n_splits = 0;
-    SnapWin* d_win = nullptr;              // in d_tokmap: bitmap | lane outs | windows | entry tables
-    SnapEnt* d_ent = nullptr;
-    const uint32_t* d_last_splits = nullptr;   // diagnostics: last pf_snappy_decompress tables
-    uint32_t* d_lane_out = nullptr;
-    std::vector<int64_t> host_status;      // per chunk host-side planning errors
+    pf::BatchPlan plan;                    // the last pf_decode_row_group's tables, lists and layout
+    // diagnostics: tables of the last pf_snappy_decompress (pf_debug_snappy_tables)
+    const uint32_t* d_last_splits = nullptr;
+    const SnapWin* d_last_win = nullptr;
+    const uint32_t* d_last_lane_out = nullptr;
     std::vector<pf_column_info> info;
-    size_t bits_bytes = 0;
-    int n_decode_first = 0;                // l_decode: pages that will need k_decode come first
-    int n_count_flat = 0;                  // l_count: flat BYTE_ARRAY pages (k_count_flat's grid) come first
-    int n_flat_fixed = 0, n_flat_all = 0, n_null4 = 0, n_null8 = 0;   // l_flat: (page, block) pairs of k_flat_fixed,
-                                                                     // k_flat_all, k_flat_null<4>, <8>
-    size_t off_npub = 0, npub_bytes = 0;   // k_nest_lvl / k_dbp_pos window hand-overs (scratch), zeroed before the batch
-    int max_nwin = 0, max_dbp_nwin = 0;
-    size_t out_bytes = 0;                  // values / offsets / levels arena extent of the last decode
-    size_t off_chunks = 0, off_pages = 0, off_jobs = 0, off_lists = 0, off_res = 0, meta_bytes = 0;
-    size_t off_pieces = 0, off_splits = 0, off_fallback = 0, off_wins = 0, off_bajobs = 0, off_batiles = 0, off_nfbq = 0;
+    bool meta_by_kernel = false;   // this batch's metadata went up by k_upload (which also zeroes bits / npub)
     uint64_t chars_need = 0;
-    const uint8_t* d_bytes = nullptr;
     int reruns = 0;
 };
 
@@ -267,48 +211,29 @@ int fail(pf_ctx* ctx, int code, const std::string& msg) {
         if ((ctx)->timing) HIPCHK(ctx, hipEventRecord(ev, st)); \
     } while (0)
 
-int type_width(int ptype, int type_length) {
-    switch (ptype) {
-    case PF_BOOLEAN: return 1;
-    case PF_INT32: case PF_FLOAT: return 4;
-    case PF_INT64: case PF_DOUBLE: return 8;
-    case PF_INT96: return 12;
-    case PF_BYTE_ARRAY: return 0;
-    case PF_FIXED_LEN_BYTE_ARRAY: return type_length > 0 ? type_length : -1;
-    default: return -1;
-    }
-}
+// k_count / k_decode blocks when no page is known to need them: both stride over their whole list,
+// and nearly every page was taken by another kernel (k_count_flat, the flat kernels)
+constexpr int COUNT_IDLE_GRID = 64;
+constexpr int DECODE_IDLE_GRID = 32;
 
 // Enqueue the kernels of the planned batch (metadata already on device).
 int enqueue_kernels(pf_ctx* ctx) {
     hipStream_t st = ctx->stream;
+    const BatchPlan& p = ctx->plan;
     uint8_t* meta = static_cast<uint8_t*>(ctx->d_meta.p);
-    DevChunk* d_chunks = reinterpret_cast<DevChunk*>(meta + ctx->off_chunks);
-    DevPage* d_pages = reinterpret_cast<DevPage*>(meta + ctx->off_pages);
-    SnappyJob* d_jobs = reinterpret_cast<SnappyJob*>(meta + ctx->off_jobs);
-    DevChunkResult* d_res = reinterpret_cast<DevChunkResult*>(meta + ctx->off_res);
-    int* lists = reinterpret_cast<int*>(meta + ctx->off_lists);
-    size_t lo = 0;
-    int* d_dictbin = lists + lo; lo += ctx->l_dictbin.size();
-    int* d_delta = lists + lo; lo += ctx->l_delta.size();
-    int* d_count = lists + lo; lo += ctx->l_count.size();
-    int* d_scan = lists + lo; lo += ctx->l_scan.size();
-    int* d_flat = lists + lo; lo += ctx->l_flat.size();
-    int* d_decode = lists + lo; lo += ctx->l_decode.size();
-    int* d_runs = lists + lo; lo += ctx->l_runs.size();
-    int* d_dlen = lists + lo; lo += ctx->l_dlen.size();
-    int* d_dba = lists + lo; lo += ctx->l_dba.size();
-    int* d_lvl = lists + lo; lo += ctx->l_lvl.size();
-    int* d_djobs = lists + lo; lo += ctx->l_djobs.size();
-    int* d_nest = lists + lo; lo += ctx->l_nest.size();
-    const int2* d_nseg = reinterpret_cast<const int2*>(lists + lo); lo += ctx->l_nseg.size();
-    const int2* d_cdict = reinterpret_cast<const int2*>(lists + lo); lo += ctx->l_cdict.size();
-    const int n_nest = int(ctx->l_nest.size()), n_nseg = int(ctx->l_nseg.size() / 2);
-    unsigned long long* used = reinterpret_cast<unsigned long long*>(meta + ctx->meta_bytes - 256);
-    const int2* d_pieces = reinterpret_cast<const int2*>(meta + ctx->off_pieces);
-    uint32_t* d_splits = reinterpret_cast<uint32_t*>(meta + ctx->off_splits);
-    int* d_fallback = reinterpret_cast<int*>(meta + ctx->off_fallback);
-    const int2* d_wins = reinterpret_cast<const int2*>(meta + ctx->off_wins);
+    DevChunk* d_chunks = reinterpret_cast<DevChunk*>(meta + p.off_chunks);
+    DevPage* d_pages = reinterpret_cast<DevPage*>(meta + p.off_pages);
+    SnappyJob* d_jobs = reinterpret_cast<SnappyJob*>(meta + p.off_jobs);
+    DevChunkResult* d_res = reinterpret_cast<DevChunkResult*>(meta + p.off_res);
+    auto list = [&](ListId l) { return reinterpret_cast<int*>(meta + p.off_lists) + p.list_base[l]; };
+    auto pairs = [&](ListId l) { return reinterpret_cast<const int2*>(list(l)); };
+    auto len = [&](ListId l) { return int(p.lists[l].size()); };
+    const int n_jobs = int(p.jobs.size()), n_nest = len(L_NEST), n_nseg = len(L_NSEG) / 2;
+    unsigned long long* used = reinterpret_cast<unsigned long long*>(meta + p.meta_bytes - 256);
+    const int2* d_pieces = reinterpret_cast<const int2*>(meta + p.off_pieces);
+    uint32_t* d_splits = reinterpret_cast<uint32_t*>(meta + p.off_splits);
+    int* d_fallback = reinterpret_cast<int*>(meta + p.off_fallback);
+    const int2* d_wins = reinterpret_cast<const int2*>(meta + p.off_wins);
 
     // diagnostics build only (bench analysis, results are wrong): stages left out of every batch, so a
     // step's time without them shows what they cost under load
@@ -318,72 +243,59 @@ int enqueue_kernels(pf_ctx* ctx) {
     constexpr unsigned skip = 0;
 #endif
     if (!ctx->meta_by_kernel) {   // (the zero-copy upload, k_upload, zeroes them)
-        if (ctx->bits_bytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_bits.p, 0, ctx->bits_bytes, st));
-        if (ctx->npub_bytes)
-            HIPCHK(ctx, hipMemsetAsync(static_cast<uint8_t*>(ctx->d_scratch.p) + ctx->off_npub, 0, ctx->npub_bytes, st));
+        if (p.bits_bytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_bits.p, 0, p.bits_bytes, st));
+        if (p.npub_bytes) HIPCHK(ctx, hipMemsetAsync(static_cast<uint8_t*>(ctx->d_scratch.p) + p.off_npub, 0, p.npub_bytes, st));
     }
     EVREC(ctx, ctx->ev[1], st);
     // single-literal pages in place, PLAIN fixed-width pages straight into the column (pf_pages.hip)
-    if (!(skip & 1u)) launch_snappy_head(d_jobs, int(ctx->jobs.size()), d_pages, d_chunks, d_fallback, d_res, st);
-    if (!(skip & 1u)) launch_snappy_litcopy(d_jobs, d_djobs, int(ctx->l_djobs.size()), d_fallback, st);
-    if (!(skip & 1u)) launch_snappy_parse(d_jobs, int(ctx->jobs.size()), d_wins, int(ctx->wins.size()), ctx->d_win, ctx->d_ent,
-                        ctx->d_lane_out, d_splits, d_fallback, ctx->max_snap_win, st);
+    if (!(skip & 1u)) launch_snappy_head(d_jobs, n_jobs, d_pages, d_chunks, d_fallback, d_res, st);
+    if (!(skip & 1u)) launch_snappy_litcopy(d_jobs, list(L_DJOBS), len(L_DJOBS), d_fallback, st);
+    if (!(skip & 1u)) launch_snappy_parse(d_jobs, n_jobs, d_wins, int(p.snap.wins.size()), p.snap.d_win, p.snap.d_ent,
+                        p.snap.d_lane_out, d_splits, d_fallback, p.snap.max_snap_win, st);
     EVREC(ctx, ctx->ev[2], st);
-    if (skip & 2u) {
-    } else if (ctx->exec_stream) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->exec_stream, ctx->ev_fork, 0));
-        launch_snappy_exec(d_jobs, int(ctx->jobs.size()), d_pieces, int(ctx->pieces.size()), d_splits, d_fallback, d_res,
-                           ctx->opts.exec, ctx->exec_stream);
-        HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->exec_stream));
-        HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-    } else {
-        launch_snappy_exec(d_jobs, int(ctx->jobs.size()), d_pieces, int(ctx->pieces.size()), d_splits, d_fallback, d_res,
-                           ctx->opts.exec, st);
-    }
+    if (!(skip & 2u))
+        launch_snappy_exec(d_jobs, n_jobs, d_pieces, int(p.snap.pieces.size()), d_splits, d_fallback, d_res, ctx->opts.exec, st);
     EVREC(ctx, ctx->ev[3], st);
-    BaJob* d_bajobs = reinterpret_cast<BaJob*>(meta + ctx->off_bajobs);
-    const int2* d_batiles = reinterpret_cast<const int2*>(meta + ctx->off_batiles);
-    const int n_ba = int(ctx->bajobs.size()), n_bt = int(ctx->ba_tiles.size());
-    (void)d_dictbin;
-    if (!(skip & 4u)) launch_ba(d_bajobs, ctx->n_ba_dict, d_batiles, ctx->n_ba_dict_tiles, d_res, st, ctx->ba_short_dict && ctx->opts.ba_fused);
+    BaJob* d_bajobs = reinterpret_cast<BaJob*>(meta + p.off_bajobs);
+    const int2* d_batiles = reinterpret_cast<const int2*>(meta + p.off_batiles);
+    const int n_ba = int(p.bajobs.size()), n_bt = int(p.ba_tiles.size());
+    if (!(skip & 4u)) launch_ba(d_bajobs, p.n_ba_dict, d_batiles, p.n_ba_dict_tiles, d_res, st, p.ba_short_dict && ctx->opts.ba_fused);
     EVREC(ctx, ctx->ev[4], st);
-    launch_delta(d_chunks, d_pages, d_delta, int(ctx->l_delta.size()), ctx->max_dbp_nwin, d_res, st);
+    launch_delta(d_chunks, d_pages, list(L_DELTA), len(L_DELTA), p.max_dbp_nwin, d_res, st);
     EVREC(ctx, ctx->ev[5], st);
-    if (!(skip & 8u)) launch_runs(d_chunks, d_pages, d_runs, int(ctx->l_runs.size()), d_res, st);
-    const NullCaps ncaps{ctx->opts.null_dcap ? ctx->opts.null_dcap : ctx->null_dcap, ctx->null_icap,
-                         ctx->opts.null_dict_lds ? ctx->null_dict_lds : 0u};
-    if (!(skip & 8u)) launch_lvl(d_chunks, d_pages, d_lvl, int(ctx->l_lvl.size()), d_res, st, ctx->opts.page_null, ncaps);
-    launch_dlen(d_chunks, d_pages, d_dlen, int(ctx->l_dlen.size()), d_res, st);
+    if (!(skip & 8u)) launch_runs(d_chunks, d_pages, list(L_RUNS), len(L_RUNS), d_res, st);
+    NullCaps ncaps = p.null_caps;
+    if (ctx->opts.null_dcap) ncaps.dcap = ctx->opts.null_dcap;
+    if (!(skip & 8u)) launch_lvl(d_chunks, d_pages, list(L_LVL), len(L_LVL), d_res, st, ctx->opts.page_null, ncaps);
+    launch_dlen(d_chunks, d_pages, list(L_DLEN), len(L_DLEN), d_res, st);
     EVREC(ctx, ctx->ev[6], st);
-    launch_nest_lvl(d_chunks, d_pages, d_nest, n_nest, ctx->max_nwin, d_res, st, ctx->opts.nest_timeout);
-    if (!(skip & 16u)) launch_count(d_chunks, d_pages, d_count, int(ctx->l_count.size()), ctx->n_count_flat, d_cdict, int(ctx->l_cdict.size() / 2),
-                                       d_res, d_bajobs, st, ctx->opts.count_grid);
-    launch_nest_count(d_chunks, d_pages, d_nest, n_nest, d_nseg, n_nseg, d_res, st);
+    launch_nest_lvl(d_chunks, d_pages, list(L_NEST), n_nest, p.max_nwin, d_res, st, ctx->opts.nest_timeout);
+    if (!(skip & 16u)) launch_count(d_chunks, d_pages, list(L_COUNT), len(L_COUNT), p.n_count_flat, pairs(L_CDICT), len(L_CDICT) / 2,
+                                       d_res, d_bajobs, st, COUNT_IDLE_GRID);
+    launch_nest_count(d_chunks, d_pages, list(L_NEST), n_nest, pairs(L_NSEG), n_nseg, d_res, st);
     if (!(skip & 4u))
-        launch_ba(d_bajobs + ctx->n_ba_dict, n_ba - ctx->n_ba_dict, d_batiles + ctx->n_ba_dict_tiles, n_bt - ctx->n_ba_dict_tiles,
-                  d_res, st, ctx->ba_short_data && ctx->opts.ba_fused);
+        launch_ba(d_bajobs + p.n_ba_dict, n_ba - p.n_ba_dict, d_batiles + p.n_ba_dict_tiles, n_bt - p.n_ba_dict_tiles,
+                  d_res, st, p.ba_short_data && ctx->opts.ba_fused);
     EVREC(ctx, ctx->ev[7], st);
-    launch_scan(d_chunks, d_pages, d_scan, int(ctx->l_scan.size()), d_res, static_cast<uint8_t*>(ctx->d_chars.p),
+    launch_scan(d_chunks, d_pages, list(L_SCAN), len(L_SCAN), d_res, static_cast<uint8_t*>(ctx->d_chars.p),
                 ctx->d_chars.cap, used, st);
     EVREC(ctx, ctx->ev[8], st);
     if (!(skip & 32u))
-        launch_flat(d_chunks, d_pages, d_flat, ctx->n_flat_fixed, ctx->n_flat_all, ctx->n_null4, ctx->n_null8,
-                    reinterpret_cast<int*>(meta + ctx->off_nfbq), d_res, st, ncaps, ctx->opts.null_stagger);
+        launch_flat(d_chunks, d_pages, list(L_FLAT), p.n_flat_fixed, p.n_flat_all, p.n_null4, p.n_null8,
+                    reinterpret_cast<int*>(meta + p.off_nfbq), d_res, st, ncaps, ctx->opts.null_stagger);
     EVREC(ctx, ctx->ev[9], st);
-    if (!(skip & 64u)) launch_decode(d_chunks, d_pages, d_decode, int(ctx->l_decode.size()), ctx->n_decode_first, d_res, st,
-                                       ctx->opts.decode_grid);
-    launch_nest_decode(d_chunks, d_pages, d_nseg, n_nseg, d_res, st);
-    launch_dba_chars(d_chunks, d_pages, d_dba, int(ctx->l_dba.size()), d_res, st);
+    if (!(skip & 64u)) launch_decode(d_chunks, d_pages, list(L_DECODE), len(L_DECODE), p.n_decode_first, d_res, st, DECODE_IDLE_GRID);
+    launch_nest_decode(d_chunks, d_pages, pairs(L_NSEG), n_nseg, d_res, st);
+    launch_dba_chars(d_chunks, d_pages, list(L_DBA), len(L_DBA), d_res, st);
     EVREC(ctx, ctx->ev[10], st);
     HIPCHK(ctx, hipGetLastError());
     // results + device-written chunk fields (chars base) back to pinned host memory
     const size_t res_pad = align_up(sizeof(DevChunkResult) * ctx->n_chunks, 256);
     if (ctx->zc && ctx->h_res.d) {
-        copy_words(ctx->h_res.d, meta + ctx->off_res, sizeof(DevChunkResult) * ctx->n_chunks,
+        copy_words(ctx->h_res.d, meta + p.off_res, sizeof(DevChunkResult) * ctx->n_chunks,
                    static_cast<uint8_t*>(ctx->h_res.d) + res_pad, d_chunks, sizeof(DevChunk) * ctx->n_chunks, st);
     } else {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_res.p, meta + ctx->off_res, sizeof(DevChunkResult) * ctx->n_chunks,
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_res.p, meta + p.off_res, sizeof(DevChunkResult) * ctx->n_chunks,
                                    hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_res.p) + res_pad, d_chunks, sizeof(DevChunk) * ctx->n_chunks,
                                    hipMemcpyDeviceToHost, st));
@@ -392,127 +304,77 @@ int enqueue_kernels(pf_ctx* ctx) {
     return PF_OK;
 }
 
-// Snappy tables of the batch's jobs: 8 KiB index windows and 64 KiB pieces. d_tokmap holds, per
-// window, 1 KiB of token-start bitmap, then 64 lane output counts, then the SnapWin records;
-// the index pass writes every word, so nothing needs clearing.
-int plan_snappy(pf_ctx* ctx) {
-    ctx->wins.clear();
-    ctx->pieces.clear();
-    ctx->n_splits = 0;
-    ctx->max_snap_win = 1;
-    uint32_t n_win = 0;
-    size_t tw = 0, tp = 0;
-    for (SnappyJob& jb : ctx->jobs) {
-        jb.n_win = std::max<uint32_t>(1u, uint32_t((uint64_t(jb.src_len) + SNAP_WIN - 1) / SNAP_WIN));
-        ctx->max_snap_win = std::max(ctx->max_snap_win, int(std::min<uint32_t>(jb.n_win, 1u << 20)));
-        jb.n_pieces = std::max<uint32_t>(1u, uint32_t((uint64_t(jb.dst_len) + SNAP_BLOCK - 1) / SNAP_BLOCK));
-        tw += jb.n_win;
-        tp += jb.n_pieces;
-    }
-    ctx->wins.resize(tw);
-    ctx->pieces.resize(tp);
-    // Dispatch the pieces with the most compressed bytes per 64 KiB of output first (more tokens per
-    // piece -> more executor steps), so the longest pieces do not start last (k_snappy_exec alone
-    // 1.50 -> 1.39 ms per launch on SF1). PF_PIECE_ORDER=0 keeps page order (A/B).
-    const bool lpt = ctx->opts.piece_order;
-    std::vector<uint64_t> keyed(lpt ? tp : 0);
-    size_t wi = 0, pi = 0;
-    for (size_t j = 0; j < ctx->jobs.size(); j++) {
-        SnappyJob& jb = ctx->jobs[j];
-        jb.win_base = n_win;
-        for (uint32_t w = 0; w < jb.n_win; w++) ctx->wins[wi++] = int2{int(j), int(w)};
-        n_win += jb.n_win;
-        jb.split_base = ctx->n_splits;
-        ctx->n_splits += jb.n_pieces;
-        const uint64_t cost = uint64_t(jb.src_len) / jb.n_pieces;   // compressed bytes per piece
-        for (uint32_t k = 0; k < jb.n_pieces; k++) {
-            if (lpt) keyed[pi] = (std::min<uint64_t>(cost, 0xffffffffull) << 32) | uint64_t(pi);
-            ctx->pieces[pi++] = int2{int(j), int(k)};
-        }
-    }
-    if (lpt) {   // descending cost in 64-byte buckets (counting sort: O(pieces)), ties in page order
-        constexpr uint32_t NB = 4096;
-        std::vector<uint32_t> start(NB + 1, 0);
-        auto bucket = [](uint64_t k) { return NB - 1 - uint32_t(std::min<uint64_t>((k >> 32) >> 6, NB - 1)); };
-        for (size_t i = 0; i < tp; i++) start[bucket(keyed[i]) + 1]++;
-        for (uint32_t b = 0; b < NB; b++) start[b + 1] += start[b];
-        std::vector<int2> sorted(tp);
-        for (size_t i = 0; i < tp; i++) sorted[start[bucket(keyed[i])]++] = ctx->pieces[size_t(uint32_t(keyed[i]))];
-        ctx->pieces.swap(sorted);
-    }
-    const size_t tok_bytes = size_t(n_win) * SNAP_WWORDS * 4, lo_bytes = size_t(n_win) * 64 * 4;
-    const size_t win_bytes = align_up(size_t(n_win) * sizeof(SnapWin), 256), ent_bytes = size_t(n_win) * 64 * sizeof(SnapEnt);
-    HIPCHK(ctx, ctx->d_tokmap.ensure(tok_bytes + lo_bytes + win_bytes + ent_bytes + 256));
-    uint8_t* base = static_cast<uint8_t*>(ctx->d_tokmap.p);
-    ctx->d_lane_out = reinterpret_cast<uint32_t*>(base + tok_bytes);
-    ctx->d_win = reinterpret_cast<SnapWin*>(base + tok_bytes + lo_bytes);
-    ctx->d_ent = reinterpret_cast<SnapEnt*>(base + tok_bytes + lo_bytes + win_bytes);
-    for (SnappyJob& jb : ctx->jobs) jb.tokmap = reinterpret_cast<uint32_t*>(base) + size_t(jb.win_base) * SNAP_WWORDS;
-    return PF_OK;
-}
-
 // Upload metadata tables (results zeroed, arena counter zeroed).
 int upload_meta(pf_ctx* ctx) {
+    const BatchPlan& p = ctx->plan;
     uint8_t* h = static_cast<uint8_t*>(ctx->h_meta.p);
-    std::memset(h, 0, ctx->meta_bytes);
-    std::memcpy(h + ctx->off_chunks, ctx->chunks.data(), sizeof(DevChunk) * ctx->chunks.size());
-    std::memcpy(h + ctx->off_pages, ctx->pages.data(), sizeof(DevPage) * ctx->pages.size());
-    std::memcpy(h + ctx->off_jobs, ctx->jobs.data(), sizeof(SnappyJob) * ctx->jobs.size());
-    std::memcpy(h + ctx->off_pieces, ctx->pieces.data(), sizeof(int2) * ctx->pieces.size());
-    std::memset(h + ctx->off_splits, 0xff, sizeof(uint32_t) * ctx->n_splits);
-    std::memcpy(h + ctx->off_wins, ctx->wins.data(), sizeof(int2) * ctx->wins.size());
-    {   // data-page walks report their chars into the page record
-        BaJob* bj = reinterpret_cast<BaJob*>(h + ctx->off_bajobs);
-        std::memcpy(bj, ctx->bajobs.data(), sizeof(BaJob) * ctx->bajobs.size());
-        uint8_t* dpages = static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_pages;
-        for (size_t i = size_t(ctx->n_ba_dict); i < ctx->bajobs.size(); i++)
-            bj[i].chars_out = reinterpret_cast<int64_t*>(dpages + sizeof(DevPage) * size_t(bj[i].page) + offsetof(DevPage, n_chars));
-        std::memcpy(h + ctx->off_batiles, ctx->ba_tiles.data(), sizeof(int2) * ctx->ba_tiles.size());
-    }
-    int* lists = reinterpret_cast<int*>(h + ctx->off_lists);
-    size_t lo = 0;
-    for (auto* v : {&ctx->l_dictbin, &ctx->l_delta, &ctx->l_count, &ctx->l_scan, &ctx->l_flat, &ctx->l_decode, &ctx->l_runs,
-                    &ctx->l_dlen, &ctx->l_dba, &ctx->l_lvl, &ctx->l_djobs, &ctx->l_nest, &ctx->l_nseg, &ctx->l_cdict}) {
-        std::copy(v->begin(), v->end(), lists + lo);
-        lo += v->size();
-    }
+    auto put = [&](size_t off, const auto& v) { if (!v.empty()) std::memcpy(h + off, v.data(), sizeof(v[0]) * v.size()); };
+    std::memset(h, 0, p.meta_bytes);
+    put(p.off_chunks, p.chunks);
+    put(p.off_pages, p.pages);
+    put(p.off_jobs, p.jobs);
+    put(p.off_pieces, p.snap.pieces);
+    std::memset(h + p.off_splits, 0xff, sizeof(uint32_t) * p.snap.n_splits);
+    put(p.off_wins, p.snap.wins);
+    put(p.off_bajobs, p.bajobs);
+    put(p.off_batiles, p.ba_tiles);
+    for (int l = 0; l < N_LISTS; l++) put(p.off_lists + sizeof(int) * p.list_base[l], p.lists[l]);
     {   // diagnostics: force_serial = k sends every k-th Snappy job to the serial kernel (tests of
         // k_snappy_serial's grid-stride over many jobs; valid streams never fall back)
         const int k = ctx->opts.force_serial;
-        int* fbh = reinterpret_cast<int*>(h + ctx->off_fallback);
+        int* fbh = reinterpret_cast<int*>(h + p.off_fallback);
         if (k > 0)
-            for (size_t j = 0; j < ctx->jobs.size(); j++)
+            for (size_t j = 0; j < p.jobs.size(); j++)
                 if (int(j % size_t(k)) == k - 1) fbh[j] = FB_SERIAL;
         // force_redo = k: the block-parallel executor rejects every k-th job (after k_snappy_head), so
         // direct pages are also decoded through the redo path (tests)
         const int kr = ctx->opts.force_redo;
-        SnappyJob* jh = reinterpret_cast<SnappyJob*>(h + ctx->off_jobs);
+        SnappyJob* jh = reinterpret_cast<SnappyJob*>(h + p.off_jobs);
         if (kr > 0)
-            for (size_t j = 0; j < ctx->jobs.size(); j++)
+            for (size_t j = 0; j < p.jobs.size(); j++)
                 if (int(j % size_t(kr)) == kr - 1) jh[j].dflags |= 1u;
     }
-    DevChunkResult* r = reinterpret_cast<DevChunkResult*>(h + ctx->off_res);
-    for (int c = 0; c < ctx->n_chunks; c++) {
-        r[c].status = int32_t(ctx->host_status[c]);
+    DevChunkResult* r = reinterpret_cast<DevChunkResult*>(h + p.off_res);
+    for (int c = 0; c < p.n_chunks; c++) {
+        r[c].status = int32_t(p.host_status[c]);
         r[c].err_page = -1;
-        const DevChunk& ck = ctx->chunks[c];
+        const DevChunk& ck = p.chunks[c];
         if (!ck.needs_count) {   // flat fixed width: slots = rows = entries (host-known)
             r[c].num_slots = ck.num_entries;
             r[c].num_rows = ck.num_entries;
         }
     }
     // k_upload counts in 32 bits: an arena of 4 GiB or more takes the copy path (its zero fills below)
-    const bool small = ctx->meta_bytes / 8 < (1ull << 31) && ctx->bits_bytes < (1ull << 31) && ctx->npub_bytes < (1ull << 31);
+    const bool small = p.meta_bytes / 8 < (1ull << 31) && p.bits_bytes < (1ull << 31) && p.npub_bytes < (1ull << 31);
     ctx->meta_by_kernel = ctx->zc && ctx->h_meta.d && small;
     if (ctx->meta_by_kernel) {   // enqueue_kernels follows at once on the same stream
-        const uint32_t n = uint32_t(ctx->meta_bytes / 8), nz0 = uint32_t(ctx->bits_bytes), nz1 = uint32_t(ctx->npub_bytes);
+        const uint32_t n = uint32_t(p.meta_bytes / 8), nz0 = uint32_t(p.bits_bytes), nz1 = uint32_t(p.npub_bytes);
         const uint32_t grid = std::max(1u, std::min(1024u, (n + (nz0 + 7u) / 8u + (nz1 + 7u) / 8u + 255u) / 256u));
         hipLaunchKernelGGL(k_upload, dim3(grid), dim3(256), 0, ctx->stream, static_cast<uint64_t*>(ctx->d_meta.p),
                            static_cast<const uint64_t*>(ctx->h_meta.d), n, static_cast<uint8_t*>(ctx->d_bits.p), nz0,
-                           static_cast<uint8_t*>(ctx->d_scratch.p) + ctx->off_npub, nz1);
+                           static_cast<uint8_t*>(ctx->d_scratch.p) + p.off_npub, nz1);
         HIPCHK(ctx, hipGetLastError());
     } else {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_meta.p, h, ctx->meta_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_meta.p, h, p.meta_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return PF_OK;
+}
+
+// Start the copy of the batch's host bytes into d_in.
+int input_to_device(pf_ctx* ctx, const uint8_t* bytes, size_t n_bytes) {
+    HIPCHK(ctx, ctx->d_in.ensure(n_bytes));
+    // pinned pages with a 16-byte aligned device address: read by a kernel (k_download's loop), so the
+    // link runs both ways at once beside the downloads (an SDMA H2D waited behind them, r06 trace)
+    void* hd = nullptr;
+    if (ctx->opts.h2d_kernel && hipHostGetDevicePointer(&hd, const_cast<uint8_t*>(bytes), 0) == hipSuccess && hd &&
+        (reinterpret_cast<uintptr_t>(hd) & 15u) == 0) {
+        const DlRange r0{static_cast<uint8_t*>(ctx->d_in.p), static_cast<const uint8_t*>(hd), uint64_t(n_bytes)};
+        const DlRange rz{nullptr, nullptr, 0};
+        hipLaunchKernelGGL(k_download, dim3(ctx->opts.h2d_grid), dim3(256), 0, ctx->stream, r0, rz, rz);
+        HIPCHK(ctx, hipGetLastError());
+    } else {
+        (void)hipGetLastError();
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_in.p, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     return PF_OK;
 }
@@ -888,11 +750,9 @@ void opts_from_env(pf::PfOpts& o) {
     o.exec = num("PF_EXEC", o.exec);
     o.ba_fused = on("PF_BA_FUSED", o.ba_fused);
     o.page_null = on("PF_PAGE_NULL", o.page_null);
-    o.null_dict_lds = on("PF_NULL_DICT_LDS", o.null_dict_lds);
     o.nest_timeout = on("PF_DEBUG_NEST_TIMEOUT", o.nest_timeout);
     o.null_dcap = uint32_t(std::max(0, num("PF_NULL_DCAP", 0))) & ~15u;
     o.null_stagger = num("PF_DEBUG_NULL_STAGGER", o.null_stagger);
-    o.piece_order = on("PF_PIECE_ORDER", o.piece_order);
     if (const char* e = std::getenv("PF_DEBUG_SKIP")) {
         const char* names[] = {"parse", "exec", "ba", "levels", "count", "flat", "decode"};
         for (int i = 0; i < 7; i++)
@@ -900,7 +760,6 @@ void opts_from_env(pf::PfOpts& o) {
     }
     o.force_serial = num("PF_DEBUG_FORCE_SERIAL", o.force_serial);
     o.force_redo = num("PF_DEBUG_FORCE_REDO", o.force_redo);
-    o.exec_stream = on("PF_EXEC_STREAM", o.exec_stream);
     o.zc = on("PF_ZC", o.zc);
     o.dl_kernel = on("PF_DL_KERNEL", o.dl_kernel);
     o.dl_stream = on("PF_DL_STREAM", o.dl_stream);
@@ -913,8 +772,6 @@ void opts_from_env(pf::PfOpts& o) {
         o.nest_seg_set = true;
     }
     o.dbp_par = on("PF_DBP_PAR", o.dbp_par);
-    o.decode_grid = std::max(1, num("PF_DECODE_GRID", o.decode_grid));
-    o.count_grid = std::max(1, num("PF_COUNT_GRID", o.count_grid));
     const int fb = num("PF_FIX_BLK", 8192);
     o.fix_shift = fb >= 16384 ? 2 : (fb >= 8192 ? 1 : 0);
 }
@@ -930,22 +787,10 @@ int ctx_init(pf_ctx* ctx, pf_ctx* peer) {
     } else {
         ctx->streams = std::make_shared<Streams>();
         ctx->streams->device = ctx->device;
-        if (ctx->opts.exec_stream) {
-            int least = 0, greatest = 0;
-            HIPCHK(nullptr, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(nullptr, hipStreamCreateWithPriority(&ctx->streams->stream, hipStreamNonBlocking, greatest));
-            HIPCHK(nullptr, hipStreamCreateWithPriority(&ctx->streams->exec_stream, hipStreamNonBlocking, least));
-        } else {
-            HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->streams->stream, hipStreamNonBlocking));
-        }
+        HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->streams->stream, hipStreamNonBlocking));
     }
     ctx->stream = ctx->streams->stream;
-    ctx->exec_stream = ctx->streams->exec_stream;
     ctx->zc = ctx->opts.zc;
-    if (ctx->exec_stream) {
-        HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    }
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_copy, hipEventDisableTiming));
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_dl, hipEventDisableTiming));
@@ -995,7 +840,6 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     if (!ctx) return PF_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // this context's work and any peer's ahead of it
-    if (ctx->exec_stream) (void)hipStreamSynchronize(ctx->exec_stream);
     if (ctx->copies_pending) (void)hipEventSynchronize(ctx->ev_copy);   // (a download on the copy stream)
     for (DevBuf* b : {&ctx->d_in, &ctx->d_scratch, &ctx->d_out, &ctx->d_bits, &ctx->d_chars, &ctx->d_meta, &ctx->d_tokmap,
                       &ctx->d_scan_in, &ctx->d_scan, &ctx->d_enc, &ctx->d_enc_sec, &ctx->d_enc_out})
@@ -1004,12 +848,10 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_res.release();
     ctx->h_enc_slots.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
     if (ctx->ev_dl) (void)hipEventDestroy(ctx->ev_dl);
-    ctx->streams.reset();   // destroys the stream(s) when no other context shares them
+    ctx->streams.reset();   // destroys the streams when no other context shares them
     delete ctx;
     return PF_OK;
 }
@@ -1051,505 +893,53 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // diagnostics: PF_DEBUG_PLAN=1 prints the host time of each planning phase (microseconds)
+    // diagnostics: PF_DEBUG_PLAN=1 prints the host time of each phase (microseconds)
     const bool dbg_plan = ctx->opts.debug_plan;
     using clk = std::chrono::steady_clock;
-    clk::time_point tp[8];
+    clk::time_point tp[7];
     int ntp = 0;
-    auto mark = [&]() { if (dbg_plan && ntp < 8) tp[ntp++] = clk::now(); };
+    auto mark = [&]() { if (dbg_plan) tp[ntp++] = clk::now(); };
     mark();
+    BatchPlan& p = ctx->plan;
     ctx->n_chunks = n_chunks;
-    ctx->chunks.assign(n_chunks, DevChunk{});
-    ctx->pages.clear(); ctx->jobs.clear();
-    ctx->l_dictbin.clear(); ctx->l_delta.clear(); ctx->l_count.clear(); ctx->l_scan.clear(); ctx->l_flat.clear(); ctx->l_decode.clear();
-    ctx->l_runs.clear(); ctx->l_dlen.clear(); ctx->l_dba.clear(); ctx->l_lvl.clear(); ctx->l_djobs.clear(); ctx->l_cdict.clear();
-    ctx->null_dict_lds = 0;
-    ctx->null_dcap = ctx->null_icap = 16;
-    ctx->l_nest.clear(); ctx->l_nseg.clear();
-    // nested pages: entries per segment (k_nest_*); PF_NEST_SEG=n (tests) sets it and sends every
-    // eligible nested page, one segment or more, down the segment path (0: none)
-    int64_t nest_seg_len = NEST_SEG;
-    bool nest_seg_forced = false;
-    if (ctx->opts.nest_seg_set) {
-        nest_seg_len = ctx->opts.nest_seg;
-        nest_seg_forced = nest_seg_len > 0;
-        if (nest_seg_len <= 0) nest_seg_len = int64_t(1) << 40;   // every page stays on k_count / k_decode
-    }
-    ctx->wins.clear(); ctx->pieces.clear(); ctx->n_splits = 0;
-    ctx->host_status.assign(n_chunks, 0);
     ctx->info.assign(n_chunks, pf_column_info{});
     ctx->reruns = 0;
     ctx->timing_valid = false;
-
-    // ---- input bytes on device ----
     // stage "h2d" (ev[0] -> ev[1]): the input copy when there is one, the metadata upload and the
     // memsets; for device-resident input it starts at the metadata upload (not before the host plan)
     const bool input_h2d = !bytes_on_device && n_bytes;
-    if (input_h2d) EVREC(ctx, ctx->ev[0], st);
     const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device && n_bytes) {
-        HIPCHK(ctx, ctx->d_in.ensure(n_bytes));
-        // pinned pages with a 16-byte aligned device address: read by a kernel (k_download's loop), so the
-        // link runs both ways at once beside the downloads (an SDMA H2D waited behind them, r06 trace)
-        void* hd = nullptr;
-        if (ctx->opts.h2d_kernel && hipHostGetDevicePointer(&hd, const_cast<uint8_t*>(bytes), 0) == hipSuccess && hd &&
-            (reinterpret_cast<uintptr_t>(hd) & 15u) == 0) {
-            const DlRange r0{static_cast<uint8_t*>(ctx->d_in.p), static_cast<const uint8_t*>(hd), uint64_t(n_bytes)};
-            const DlRange rz{nullptr, nullptr, 0};
-            hipLaunchKernelGGL(k_download, dim3(ctx->opts.h2d_grid), dim3(256), 0, st, r0, rz, rz);
-            HIPCHK(ctx, hipGetLastError());
-        } else {
-            (void)hipGetLastError();
-            HIPCHK(ctx, hipMemcpyAsync(ctx->d_in.p, bytes, n_bytes, hipMemcpyHostToDevice, st));
-        }
+    if (input_h2d) {
+        EVREC(ctx, ctx->ev[0], st);
+        const int rc = input_to_device(ctx, bytes, n_bytes);
+        if (rc) return rc;
         d_bytes = static_cast<const uint8_t*>(ctx->d_in.p);
     }
-    ctx->d_bytes = d_bytes;
-
-    // ---- plan: sizes of scratch / outputs ----
-    struct PagePlan { uint64_t scratch_off; uint64_t aux_off; int is_dict; uint64_t rt_off; uint64_t dx_off; uint64_t lt_off; uint64_t seg_off; int32_t nseg, seg_len, nwin; uint64_t pub_off; uint64_t dbp_off, dbp_pub_off; int32_t dbp_nwin; uint32_t dbp_bcap; };
-    std::vector<PagePlan> pplan;
-    size_t scratch = 0, out = 0, bits = 0;
-    uint64_t nest_pub = 0;
-    ctx->max_nwin = 0;
-    ctx->max_dbp_nwin = 0;
-    // PF_DBP_PAR=0: every DELTA_BINARY_PACKED page on the one-workgroup k_delta (tests)
-    const bool dbp_par = ctx->opts.dbp_par;
-    uint64_t chars_hint = 0;
-    struct OutPlan { size_t values, validity, offsets, list_offsets, list_validity, def, rep; };
-    std::vector<OutPlan> oplan(n_chunks);
-    auto take = [](size_t& cursor, size_t n, size_t a = 256) { size_t o = align_up(cursor, a); cursor = o + n; return o; };
-
-    for (int c = 0; c < n_chunks; c++) {
-        const pf_chunk_desc& cd = cds[c];
-        DevChunk& ck = ctx->chunks[c];
-        ck.ptype = cd.physical_type; ck.type_length = cd.type_length;
-        ck.width = type_width(cd.physical_type, cd.type_length);
-        ck.max_def = cd.max_def; ck.max_rep = cd.max_rep; ck.repeated_def = cd.repeated_def;
-        ck.list_null_def = cd.list_null_def; ck.codec = cd.codec;
-        ck.dict_page = -1;
-        ck.first_page = int(ctx->pages.size());
-        int64_t& hs = ctx->host_status[c];
-        if (ck.width < 0) hs = PF_ERR_UNSUPPORTED_TYPE;
-        else if (cd.codec != PF_CODEC_UNCOMPRESSED && cd.codec != PF_CODEC_SNAPPY) hs = PF_ERR_UNSUPPORTED_CODEC;
-        else if (cd.max_def < 0 || cd.max_def > 255 || cd.max_rep < 0 || cd.max_rep > 255 || cd.n_pages < 0 ||
-                 (cd.n_pages > 0 && !cd.pages) || cd.chunk_offset + cd.chunk_size > n_bytes)
-            hs = PF_ERR_INVALID_ARG;
-        ck.needs_count = (cd.physical_type == PF_BYTE_ARRAY || cd.max_rep > 0) ? 1 : 0;
-        int64_t entries = 0;
-        int dict_global = -1;
-        if (hs == 0) {
-            for (int i = 0; i < cd.n_pages; i++) {
-                const pf_page_desc& pd = cd.pages[i];
-                if (pd.offset + pd.compressed_size > cd.chunk_size) { hs = PF_ERR_CORRUPT_PAGE; break; }
-                if (pd.uncompressed_size > (1u << 29) || pd.compressed_size > (1u << 30)) { hs = PF_ERR_CORRUPT_PAGE; break; }
-                bool is_dict = pd.page_type == PF_PAGE_DICTIONARY;
-                bool v2 = pd.page_type == PF_PAGE_DATA_V2;
-                if (!is_dict && pd.page_type != PF_PAGE_DATA && !v2) continue;   // index pages
-                if (is_dict && (dict_global >= 0 || ck.n_pages > 0)) { hs = PF_ERR_CORRUPT_PAGE; break; }
-                DevPage pg{};
-                pg.chunk = c;
-                pg.ba_job = -1;
-                pg.encoding = pd.encoding; pg.def_enc = pd.def_encoding; pg.rep_enc = pd.rep_encoding;
-                pg.num_values = pd.num_values;
-                pg.flags = (v2 ? PG_V2 : 0) | (is_dict ? PG_DICT : 0);
-                if (pd.num_values < 0) { hs = PF_ERR_CORRUPT_PAGE; break; }
-                const uint8_t* src = d_bytes + cd.chunk_offset + pd.offset;
-                uint32_t lvl = v2 ? uint32_t(pd.rep_bytes) + uint32_t(pd.def_bytes) : 0;
-                if (v2 && (pd.rep_bytes < 0 || pd.def_bytes < 0 || lvl > pd.compressed_size || lvl > pd.uncompressed_size)) {
-                    hs = PF_ERR_CORRUPT_PAGE; break;
-                }
-                bool compressed = cd.codec == PF_CODEC_SNAPPY && (!v2 || pd.is_compressed);
-                PagePlan pp{0, ~0ull, is_dict, ~0ull, ~0ull, ~0ull, ~0ull, 0, 0, 0, 0, ~0ull, 0, 0, 0};
-                if (v2) { pg.lvl = src; pg.rep_len = uint32_t(pd.rep_bytes); pg.def_len = uint32_t(pd.def_bytes); }
-                if (compressed) {
-                    pp.scratch_off = take(scratch, pd.uncompressed_size - lvl, 16);
-                    pg.flags |= PG_COMPRESSED;
-                    pg.body_len = pd.uncompressed_size - lvl;
-                    SnappyJob j{};
-                    j.src = src + lvl; j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
-                    j.page = int(ctx->pages.size()); j.chunk = c;
-                    ctx->jobs.push_back(j);   // dst patched after scratch allocation
-                } else {
-                    pg.body = src + lvl;
-                    pg.body_len = pd.compressed_size - lvl;
-                }
-                if (is_dict) {
-                    dict_global = int(ctx->pages.size());
-                    ck.dict_page = dict_global;
-                    ck.dict_n = pd.num_values;
-                    if (pd.encoding != PF_ENC_PLAIN && pd.encoding != PF_ENC_PLAIN_DICTIONARY) { hs = PF_ERR_UNSUPPORTED_ENCODING; break; }
-                    if (cd.physical_type == PF_BOOLEAN) { hs = PF_ERR_UNSUPPORTED_ENCODING; break; }
-                    if (cd.physical_type == PF_BYTE_ARRAY) {
-                        pp.aux_off = take(scratch, 8ull * (pd.num_values + 1), 256);
-                        ctx->l_dictbin.push_back(c);
-                    } else if (uint64_t(pd.num_values) * ck.width > pg.body_len) { hs = PF_ERR_CORRUPT_PAGE; break; }
-                } else {
-                    pg.entry_start = entries;
-                    entries += pd.num_values;
-                    ck.n_pages++;
-                    if (cd.physical_type == PF_BYTE_ARRAY)   // value positions / ids + per-block chars (k_flat)
-                        pp.aux_off = take(scratch, 4ull * pd.num_values + 16 + 8ull * (uint64_t(pd.num_values) / FLAT_BLK + 2), 256);
-                    else if (pd.encoding == PF_ENC_DELTA_BINARY_PACKED && (cd.physical_type == PF_INT32 || cd.physical_type == PF_INT64)) {
-                        pp.aux_off = take(scratch, 8ull * pd.num_values + 8, 256);
-                        if (pd.num_values >= DBP_PAR_MIN && dbp_par) {   // block-parallel decode (k_dbp_*)
-                            pp.dbp_bcap = uint32_t(pd.num_values / 8 + 2);
-                            pp.dbp_off = take(scratch, 12ull * pp.dbp_bcap + 16, 256);
-                            pp.dbp_nwin = int32_t((uint64_t(std::max(pd.uncompressed_size, pd.compressed_size)) + DBP_WIN - 1) / DBP_WIN + 1);
-                            pp.dbp_pub_off = nest_pub;
-                            nest_pub += uint64_t(pp.dbp_nwin) * sizeof(WinPub);
-                        }
-                    }
-                    if (cd.physical_type == PF_BYTE_ARRAY) chars_hint += pd.uncompressed_size;
-                    if (cd.physical_type == PF_BYTE_ARRAY &&
-                        (pd.encoding == PF_ENC_DELTA_LENGTH_BYTE_ARRAY || pd.encoding == PF_ENC_DELTA_BYTE_ARRAY))
-                        pp.dx_off = take(scratch, 8ull * (3ull * uint64_t(pd.num_values) + 1), 256);   // k_dlen
-                    if (cd.max_rep == 0 && cd.physical_type != PF_BOOLEAN &&
-                        (pd.encoding == PF_ENC_PLAIN_DICTIONARY || pd.encoding == PF_ENC_RLE_DICTIONARY))
-                        pp.rt_off = take(scratch, RT_BYTES, 256);   // k_runs table
-                    if (cd.max_rep == 0 && cd.max_def > 0 && cd.physical_type != PF_BOOLEAN && cd.physical_type != PF_BYTE_ARRAY &&
-                        pd.num_nulls != 0 &&   // v2 header / v1 page statistics say when no level is null (-1: unknown)
-                        (pd.encoding == PF_ENC_PLAIN || pd.encoding == PF_ENC_PLAIN_DICTIONARY || pd.encoding == PF_ENC_RLE_DICTIONARY))
-                        pp.lt_off = take(scratch, 16 + 16ull * lvl_table_cap(pd.num_values) +
-                                                      4ull * LT_BT_WORDS * (uint64_t(pd.num_values) / FLAT_BLK + 1), 256);   // k_lvl tables
-                    {   // nested pages decoded in segments (k_nest_*): PLAIN fixed width, dictionary, DELTA_BINARY_PACKED ints
-                        const int e = pd.encoding;
-                        const bool enc_ok = (e == PF_ENC_PLAIN && cd.physical_type != PF_BYTE_ARRAY) ||
-                                            e == PF_ENC_PLAIN_DICTIONARY || e == PF_ENC_RLE_DICTIONARY ||
-                                            (e == PF_ENC_DELTA_BINARY_PACKED && (cd.physical_type == PF_INT32 || cd.physical_type == PF_INT64));
-                        if (cd.max_rep > 0 && cd.physical_type != PF_BOOLEAN && enc_ok && pd.num_values > 0) {
-                            const int64_t sl = std::max<int64_t>(nest_seg_len, (int64_t(pd.num_values) + NEST_MAX_SEGS - 1) / NEST_MAX_SEGS);
-                            const int64_t ns = (int64_t(pd.num_values) + sl - 1) / sl;
-                            if (ns >= 2 || nest_seg_forced) {
-                                pp.seg_len = int32_t(sl);
-                                pp.nseg = int32_t(ns);
-                                pp.seg_off = take(scratch, nest_seg_bytes(pp.nseg), 256);
-                                // windows over the longer level stream (v2: its length is in the header; v1: the page bounds it)
-                                const uint64_t lvl_bytes = v2 ? uint64_t(std::max(pd.rep_bytes, pd.def_bytes))
-                                                              : uint64_t(std::max(pd.uncompressed_size, pd.compressed_size));
-                                pp.nwin = int32_t((lvl_bytes + NEST_WIN - 1) / NEST_WIN + 1);
-                                pp.pub_off = nest_pub;   // (the window hand-overs of all pages: one block, zeroed per batch)
-                                nest_pub += 2ull * uint64_t(pp.nwin) * sizeof(WinPub);
-                            }
-                        }
-                    }
-                }
-                pplan.push_back(pp);
-                ctx->pages.push_back(pg);
-            }
-        }
-        if (hs != 0) {   // drop this chunk's pages from every list
-            while (int(ctx->pages.size()) > ck.first_page) { ctx->pages.pop_back(); pplan.pop_back(); }
-            while (!ctx->jobs.empty() && ctx->jobs.back().chunk == c) ctx->jobs.pop_back();
-            if (!ctx->l_dictbin.empty() && ctx->l_dictbin.back() == c) ctx->l_dictbin.pop_back();
-            ck.n_pages = 0; ck.dict_page = -1; entries = 0;
-        }
-        if (ck.dict_page >= 0) ck.first_page = ck.dict_page + 1;
-        ck.num_entries = entries;
-        // outputs
-        OutPlan& op = oplan[c];
-        op = OutPlan{~size_t(0), ~size_t(0), ~size_t(0), ~size_t(0), ~size_t(0), ~size_t(0), ~size_t(0)};
-        if (hs == 0) {
-            if (ck.width > 0) op.values = take(out, size_t(entries) * ck.width);
-            if (cd.max_def > 0) op.validity = take(bits, align_up((entries + 7) / 8, 4), 256);
-            if (cd.physical_type == PF_BYTE_ARRAY) op.offsets = take(out, 4 * size_t(entries + 1));
-            if (cd.max_rep == 1) {
-                op.list_offsets = take(out, 4 * size_t(entries + 1));
-                op.list_validity = take(bits, align_up((entries + 7) / 8, 4), 256);
-            }
-            if (cd.max_rep > 0) { op.def = take(out, entries); op.rep = take(out, entries); }
-        }
-    }
     mark();
-    // ---- PLAIN BYTE_ARRAY walk jobs: dictionary pages first, then PLAIN data pages ----
-    ctx->bajobs.clear();
-    ctx->ba_tiles.clear();
-    ctx->ba_short_dict = ctx->ba_short_data = true;
-    // k_ba_tile links values of up to ~124 bytes within a tile; pages of longer values would all take
-    // the exact fallback walk there, so a batch with such pages keeps the multi-kernel walk
-    constexpr uint64_t BA_SHORT = 48;
-    std::vector<size_t> ba_bm;
-    for (int pass = 0; pass < 2; pass++) {
-        for (size_t i = 0; i < ctx->pages.size(); i++) {
-            DevPage& pg = ctx->pages[i];
-            const DevChunk& ck = ctx->chunks[pg.chunk];
-            if (ck.ptype != PF_BYTE_ARRAY || ctx->host_status[pg.chunk] != 0) continue;
-            const bool is_dict = pg.flags & PG_DICT;
-            if (pass == 0 ? !is_dict : (is_dict || pg.encoding != PF_ENC_PLAIN)) continue;
-            BaJob J{};
-            J.n_cap = pg.body_len;
-            J.n_tiles = std::max<uint32_t>(1u, (pg.body_len + BA_TILE_BYTES - 1) / BA_TILE_BYTES);
-            J.chunk = pg.chunk;
-            J.page = int32_t(i);
-            J.state = BA_SKIP;
-            const size_t words = size_t(J.n_tiles) * (BA_TILE_BYTES / 32);
-            ba_bm.push_back(take(scratch, 4 * (3 * words + J.n_tiles), 256));
-            const int rel = int(ctx->bajobs.size()) - (pass == 0 ? 0 : ctx->n_ba_dict);
-            for (uint32_t t = 0; t < J.n_tiles; t++) ctx->ba_tiles.push_back(int2{rel, int(t)});
-            if (pass == 1) pg.ba_job = int32_t(ctx->bajobs.size());
-            if (uint64_t(pg.body_len) > BA_SHORT * uint64_t(std::max<int64_t>(1, pg.num_values)))
-                (pass == 0 ? ctx->ba_short_dict : ctx->ba_short_data) = false;
-            ctx->bajobs.push_back(J);
-        }
-        if (pass == 0) { ctx->n_ba_dict = int(ctx->bajobs.size()); ctx->n_ba_dict_tiles = int(ctx->ba_tiles.size()); }
-    }
+    plan_batch(cds, n_chunks, n_bytes, ctx->opts, p);
     mark();
-    // ---- allocate arenas ----
-    size_t chars_cap = std::max<size_t>(size_t(2 * chars_hint) + (16u << 20), ctx->chars_need);
+    // ---- arenas ----
+    const size_t chars_cap = std::max<size_t>(size_t(2 * p.chars_hint) + (16u << 20), ctx->chars_need);
     if (ctx->copies_pending) {
-        if (out > ctx->d_out.cap || bits > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap)
+        if (p.out_bytes > ctx->d_out.cap || p.bits_bytes > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap)
             HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // a growing output arena must not be freed under a pending D2H copy
         else
             HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_copy, 0));   // (a download on the copy stream reads the arenas)
     }
     ctx->copies_pending = false;
-    ctx->npub_bytes = size_t(nest_pub);
-    ctx->off_npub = take(scratch, ctx->npub_bytes, 256);
-    HIPCHK(ctx, ctx->d_scratch.ensure(std::max<size_t>(scratch, 1)));
-    HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(out, 1)));
-    HIPCHK(ctx, ctx->d_bits.ensure(std::max<size_t>(bits, 1)));
+    HIPCHK(ctx, ctx->d_scratch.ensure(std::max<size_t>(p.scratch_bytes, 1)));
+    HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(p.out_bytes, 1)));
+    HIPCHK(ctx, ctx->d_bits.ensure(std::max<size_t>(p.bits_bytes, 1)));
     HIPCHK(ctx, ctx->d_chars.ensure(chars_cap));
-    ctx->bits_bytes = bits;
-    ctx->out_bytes = out;
-    uint8_t* S = static_cast<uint8_t*>(ctx->d_scratch.p);
-    uint8_t* O = static_cast<uint8_t*>(ctx->d_out.p);
-    uint8_t* B = static_cast<uint8_t*>(ctx->d_bits.p);
-    {
-        size_t ji = 0;
-        for (size_t i = 0; i < ctx->pages.size(); i++) {
-            DevPage& pg = ctx->pages[i];
-            const PagePlan& pp = pplan[i];
-            if (pg.flags & PG_COMPRESSED) {
-                pg.body = S + pp.scratch_off;
-                while (ji < ctx->jobs.size() && ctx->jobs[ji].page != int(i)) ji++;
-                if (ji < ctx->jobs.size()) ctx->jobs[ji].dst = S + pp.scratch_off;
-            }
-            if (pp.aux_off != ~0ull) {
-                pg.aux = reinterpret_cast<uint32_t*>(S + pp.aux_off);
-                pg.aux_cap = pg.num_values;
-            }
-            if (pp.rt_off != ~0ull) {
-                pg.runtab = reinterpret_cast<uint32_t*>(S + pp.rt_off);
-                ctx->l_runs.push_back(int(i));
-            }
-            if (pp.lt_off != ~0ull) {
-                pg.lvltab = reinterpret_cast<uint32_t*>(S + pp.lt_off);
-                pg.lvl_cap = lvl_table_cap(pg.num_values);
-                ctx->l_lvl.push_back(int(i));
-                const DevChunk& lc = ctx->chunks[size_t(pg.chunk)];
-                const uint64_t db = uint64_t(std::max<int64_t>(lc.dict_n, 0)) * uint64_t(std::max(lc.width, 0));
-                if (lc.dict_page >= 0 && db > 0 && db <= NULL_DICT_LDS)
-                    ctx->null_dict_lds = std::max(ctx->null_dict_lds, uint32_t(align_up(db, 256)));
-                // level / id byte stages: FBLK values of the level width / the dictionary's id width
-                // (bit width of its largest index, as writers choose it) + run headers
-                auto bits = [](uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; };
-                // hybrid worst case: bit-packed, FLAT_BLK * b / 8 bytes + headers; or RLE runs of
-                // 8 repeats, a header byte + ceil(b / 8) value bytes per 8 entries (1-bit levels: 1 KiB)
-                auto cap = [](int b, uint32_t most) {
-                    const uint64_t bp = uint64_t(FLAT_BLK) * uint64_t(b) / 8;
-                    const uint64_t rle = uint64_t(FLAT_BLK) / 8 * (1 + (uint64_t(b) + 7) / 8);
-                    return uint32_t(std::min<uint64_t>(most, align_up(std::max(bp, rle) + NL_SLACK, 16)));
-                };
-                ctx->null_dcap = std::max(ctx->null_dcap, cap(bits(uint64_t(std::max(lc.max_def, 0))), NL_DST));
-                if (lc.dict_page >= 0)
-                    ctx->null_icap = std::max(ctx->null_icap, cap(bits(uint64_t(std::max<int64_t>(lc.dict_n, 1) - 1)), NL_IST));
-            }
-            if (pp.dbp_off != ~0ull) {
-                pg.dbp = S + pp.dbp_off;
-                pg.dbp_pub = reinterpret_cast<WinPub*>(S + ctx->off_npub + pp.dbp_pub_off);
-                pg.dbp_nwin = pp.dbp_nwin;
-                pg.dbp_bcap = pp.dbp_bcap;
-                ctx->max_dbp_nwin = std::max(ctx->max_dbp_nwin, pp.dbp_nwin);
-            }
-            if (pp.seg_off != ~0ull) {
-                pg.seg = S + pp.seg_off;
-                pg.nseg = pp.nseg;
-                pg.seg_len = pp.seg_len;
-                pg.nwin = pp.nwin;
-                pg.npub = reinterpret_cast<WinPub*>(S + ctx->off_npub + pp.pub_off);
-                ctx->max_nwin = std::max(ctx->max_nwin, pp.nwin);
-                ctx->l_nest.push_back(int(i));
-                for (int k = 0; k < pp.nseg; k++) { ctx->l_nseg.push_back(int(i)); ctx->l_nseg.push_back(k); }
-            }
-            if (pp.dx_off != ~0ull) {
-                pg.dx = reinterpret_cast<uint64_t*>(S + pp.dx_off);
-                ctx->l_dlen.push_back(int(i));
-                if (pg.encoding == PF_ENC_DELTA_BYTE_ARRAY) ctx->l_dba.push_back(int(i));
-            }
-            DevChunk& ck = ctx->chunks[pg.chunk];
-            if (pp.is_dict) {
-                ck.dict_data = pg.body;
-                if (ck.ptype == PF_BYTE_ARRAY) {
-                    ck.dict_pos = reinterpret_cast<uint32_t*>(S + pp.aux_off);
-                    ck.dict_len = ck.dict_pos + (pg.num_values + 1);
-                }
-            }
-        }
-    }
-    for (size_t b = 0; b < ctx->bajobs.size(); b++) {
-        BaJob& J = ctx->bajobs[b];
-        const size_t words = size_t(J.n_tiles) * (BA_TILE_BYTES / 32);
-        J.cand = reinterpret_cast<uint32_t*>(S + ba_bm[b]);
-        J.link1 = J.cand + words;
-        J.link2 = J.link1 + words;
-        J.tile_cnt = J.link2 + words;
-        const DevPage& pg = ctx->pages[J.page];
-        if (int(b) < ctx->n_ba_dict) {
-            const DevChunk& ck = ctx->chunks[J.chunk];
-            J.p = pg.body;
-            J.n = pg.body_len;
-            J.count = ck.dict_n;
-            J.pos = ck.dict_pos;
-            J.len = ck.dict_len;
-            J.state = ck.dict_n > 0 ? BA_OK : BA_SKIP;
-        } else {
-            J.pos = pg.aux;   // p, n, count, state: k_count
-        }
-    }
-    for (int c = 0; c < n_chunks; c++) {
-        DevChunk& ck = ctx->chunks[c];
-        const OutPlan& op = oplan[c];
-        auto at = [](uint8_t* base, size_t off) { return off == ~size_t(0) ? nullptr : base + off; };
-        ck.values = at(O, op.values);
-        ck.validity = at(B, op.validity);
-        ck.offsets = reinterpret_cast<int32_t*>(at(O, op.offsets));
-        ck.list_offsets = reinterpret_cast<int32_t*>(at(O, op.list_offsets));
-        ck.list_validity = at(B, op.list_validity);
-        ck.def_levels = at(O, op.def);
-        ck.rep_levels = at(O, op.rep);
-        if (ctx->host_status[c] == 0) {
-            if (ck.needs_count) ctx->l_scan.push_back(c);
-        }
-    }
-    // (page, block) pairs of the flat kernels. A chunk with a large dictionary keeps all its blocks on
-    // one blockIdx % 8 label (the dispatcher's XCD group, MI355X_MICROARCH.md), so the dictionary is
-    // gathered through one XCD's L2 instead of all eight (config 4: 400 KB dictionaries); such chunks
-    // go to the least loaded label, all other blocks then fill the labels evenly. Labels are
-    // interleaved into the grid; short ones are padded with (-1, 0).
-    // Four such grids, one after the other in l_flat: fixed-width pages (k_flat_fixed), the other flat
-    // pages (k_flat_all), then the blocks of nullable 4- and 8-byte pages (k_flat_null<4> / <8>);
-    // k_flat_fixed and k_flat_null queue what they do not take for k_flat_all's last workgroups.
-    constexpr uint32_t STICKY_DICT = 64u << 10;
-    std::vector<int> spread[4];
-    std::vector<std::vector<int>> sticky[4];
-    for (auto& v : sticky) v.resize(static_cast<size_t>(n_chunks));
-    std::vector<int> decode_first, count_rest;
-    for (size_t i = 0; i < ctx->pages.size(); i++) {
-        const DevPage& pg = ctx->pages[i];
-        if (pg.flags & PG_DICT) continue;
-        const DevChunk& ck = ctx->chunks[pg.chunk];
-        if (pg.encoding == PF_ENC_DELTA_BINARY_PACKED && pg.aux && ck.ptype != PF_BYTE_ARRAY) ctx->l_delta.push_back(int(i));
-        if (ck.needs_count) (ck.ptype == PF_BYTE_ARRAY && ck.max_rep == 0 ? ctx->l_count : count_rest).push_back(int(i));
-        if (ck.ptype == PF_BYTE_ARRAY && ck.max_rep == 0 && pg.runtab != nullptr &&
-            (pg.encoding == PF_ENC_PLAIN_DICTIONARY || pg.encoding == PF_ENC_RLE_DICTIONARY)) {
-            const int nb = std::max(1, int((int64_t(pg.num_values) + FLAT_BLK - 1) / FLAT_BLK));
-            for (int b = 0; b < nb; b++) { ctx->l_cdict.push_back(int(i)); ctx->l_cdict.push_back(b); }
-        }
-        if (ck.max_rep == 0) {   // (page, block) pairs
-            // fixed-width pages without a level table (no nulls) take blocks of FLAT_BLK << fix_shift
-            // entries (the block index carries the shift in bits 28..31): a block's metadata chain and
-            // run-table load are paid once per 8192 entries instead of per 4096 (PF_FIX_BLK=4096|8192|16384)
-            const int fix_shift = ctx->opts.fix_shift;
-            const int sh = (ck.ptype != PF_BYTE_ARRAY && pg.lvltab == nullptr) ? fix_shift : 0;
-            const int64_t bsz = FLAT_BLK << sh;
-            const int nb = std::max(1, int((int64_t(pg.num_values) + bsz - 1) / bsz));
-            const bool dict_enc = pg.encoding == PF_ENC_PLAIN_DICTIONARY || pg.encoding == PF_ENC_RLE_DICTIONARY;
-            const bool big_dict = ck.dict_page >= 0 && ctx->pages[size_t(ck.dict_page)].body_len > STICKY_DICT && dict_enc;
-            const int grid = (pg.lvltab != nullptr && ck.ptype != PF_BYTE_ARRAY && (dict_enc || pg.encoding == PF_ENC_PLAIN))
-                                 ? (ck.width == 4 ? 2 : (ck.width == 8 ? 3 : 1))
-                                 : (ck.ptype != PF_BYTE_ARRAY ? 0 : 1);
-            std::vector<int>& q = big_dict ? sticky[grid][size_t(pg.chunk)] : spread[grid];
-            for (int b = 0; b < nb; b++) { q.push_back(int(i)); q.push_back(b | (sh << 28)); }
-        }
-        // k_decode does the pages the flat kernels do not take: nested pages and encodings other than
-        // PLAIN / dictionary / DELTA_BINARY_PACKED go first (one block each), the rest are only checked
-        const int e = pg.encoding;
-        if (ck.max_rep > 0 || !(e == PF_ENC_PLAIN || e == PF_ENC_PLAIN_DICTIONARY || e == PF_ENC_RLE_DICTIONARY ||
-                                e == PF_ENC_DELTA_BINARY_PACKED) || ck.ptype == PF_BOOLEAN)
-            decode_first.push_back(int(i));
-        else
-            ctx->l_decode.push_back(int(i));
-    }
-    ctx->n_decode_first = int(decode_first.size());
-    ctx->n_count_flat = int(ctx->l_count.size());
-    ctx->l_count.insert(ctx->l_count.end(), count_rest.begin(), count_rest.end());
-    ctx->l_decode.insert(ctx->l_decode.begin(), decode_first.begin(), decode_first.end());
-    int n_grid[4] = {};
-    for (int gi = 0; gi < 4; gi++) {
-        std::vector<int> xq[8];
-        size_t load[8] = {};
-        std::vector<int> order(static_cast<size_t>(n_chunks));
-        for (int c = 0; c < n_chunks; c++) order[size_t(c)] = c;
-        const auto& sk = sticky[gi];
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sk[size_t(a)].size() > sk[size_t(b)].size(); });
-        for (int c : order) {
-            if (sk[size_t(c)].empty()) continue;
-            const int x = int(std::min_element(load, load + 8) - load);
-            xq[x].insert(xq[x].end(), sk[size_t(c)].begin(), sk[size_t(c)].end());
-            load[x] += sk[size_t(c)].size() / 2;
-        }
-        const std::vector<int>& sp = spread[gi];
-        for (size_t k = 0; k + 1 < sp.size(); k += 2) {
-            const int x = int(std::min_element(load, load + 8) - load);
-            xq[x].push_back(sp[k]);
-            xq[x].push_back(sp[k + 1]);
-            load[x]++;
-        }
-        const size_t longest = *std::max_element(load, load + 8);
-        for (size_t k = 0; k < longest; k++)
-            for (int x = 0; x < 8; x++) {
-                const bool have = k < load[x];
-                ctx->l_flat.push_back(have ? xq[x][2 * k] : -1);
-                ctx->l_flat.push_back(have ? xq[x][2 * k + 1] : 0);
-            }
-        n_grid[gi] = int(8 * longest);
-    }
-    ctx->n_flat_fixed = n_grid[0];
-    ctx->n_flat_all = n_grid[1];
-    ctx->n_null4 = n_grid[2];
-    ctx->n_null8 = n_grid[3];
-    mark();
-    // k_snappy_litcopy candidates (k_snappy_head decides): dictionary pages, and data pages that did
-    // not compress (a stream of literals only; one literal is read in place instead)
-    for (size_t j = 0; j < ctx->jobs.size(); j++) {
-        SnappyJob& jb = ctx->jobs[j];
-        if ((ctx->pages[size_t(jb.page)].flags & PG_DICT) || jb.src_len >= jb.dst_len) {
-            jb.dflags |= 2u;
-            ctx->l_djobs.push_back(int(j));
-        }
-    }
-    // ---- Snappy tables: 8 KiB index windows, 64 KiB pieces ----
-    {
-        int rc = plan_snappy(ctx);
-        if (rc) return rc;
-    }
-    mark();
-    // ---- metadata upload ----
-    size_t m = 0;
-    ctx->off_chunks = take(m, sizeof(DevChunk) * n_chunks);
-    ctx->off_pages = take(m, sizeof(DevPage) * ctx->pages.size());
-    ctx->off_jobs = take(m, sizeof(SnappyJob) * ctx->jobs.size());
-    ctx->off_lists = take(m, sizeof(int) * (ctx->l_dictbin.size() + ctx->l_delta.size() + ctx->l_count.size() +
-                                            ctx->l_scan.size() + ctx->l_flat.size() + ctx->l_decode.size() + ctx->l_runs.size() +
-                                            ctx->l_dlen.size() + ctx->l_dba.size() + ctx->l_lvl.size() + ctx->l_djobs.size() +
-                                            ctx->l_nest.size() + ctx->l_nseg.size() + ctx->l_cdict.size()));
-    ctx->off_res = take(m, sizeof(DevChunkResult) * n_chunks);
-    ctx->off_pieces = take(m, sizeof(int2) * ctx->pieces.size());
-    ctx->off_splits = take(m, sizeof(uint32_t) * ctx->n_splits);
-    ctx->off_fallback = take(m, sizeof(int) * ctx->jobs.size());
-    ctx->off_wins = take(m, sizeof(int2) * ctx->wins.size());
-    ctx->off_bajobs = take(m, sizeof(BaJob) * ctx->bajobs.size());
-    ctx->off_batiles = take(m, sizeof(int2) * ctx->ba_tiles.size());
-    ctx->off_nfbq = take(m, 16 + sizeof(int2) * size_t(ctx->n_flat_fixed + ctx->n_null4 + ctx->n_null8), 16);   // fallback queue
-    m = take(m, 256) + 256;   // arena counter lives in the last 256 bytes
-    ctx->meta_bytes = m;
-    HIPCHK(ctx, ctx->d_meta.ensure(m));
-    HIPCHK(ctx, ctx->h_meta.ensure(m));
-    {   // each Snappy data page reads its job's fallback flag (k_flat_fixed: were the values written direct?)
-        const int* d_fb = reinterpret_cast<const int*>(static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_fallback);
-        for (size_t j = 0; j < ctx->jobs.size(); j++) ctx->pages[size_t(ctx->jobs[j].page)].jfb = d_fb + j;
-    }
+    HIPCHK(ctx, ctx->d_tokmap.ensure(p.snap.tokmap_bytes));
+    HIPCHK(ctx, ctx->d_meta.ensure(p.meta_bytes));
+    HIPCHK(ctx, ctx->h_meta.ensure(p.meta_bytes));
     HIPCHK(ctx, ctx->h_res.ensure(align_up(sizeof(DevChunkResult) * n_chunks, 256) + sizeof(DevChunk) * n_chunks + 256));
+    mark();
+    auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    bind_batch(p, ArenaBases{addr(d_bytes), addr(ctx->d_scratch.p), addr(ctx->d_out.p), addr(ctx->d_bits.p), addr(ctx->d_meta.p),
+                             addr(ctx->d_tokmap.p)});
+    mark();
     if (!input_h2d) EVREC(ctx, ctx->ev[0], st);
     int rc = upload_meta(ctx);
     if (rc) return rc;
@@ -1559,8 +949,8 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
     mark();
     if (dbg_plan) {
         auto us = [&](int a, int b) { return long(std::chrono::duration_cast<std::chrono::microseconds>(tp[b] - tp[a]).count()); };
-        std::fprintf(stderr, "[pf plan] chunks %d pages %zu jobs %zu wins %zu | pages %ld ba %ld alloc+lists %ld snappy %ld meta %ld launch %ld us\n",
-                     n_chunks, ctx->pages.size(), ctx->jobs.size(), ctx->wins.size(), us(0, 1), us(1, 2), us(2, 3), us(3, 4),
+        std::fprintf(stderr, "[pf plan] chunks %d pages %zu jobs %zu wins %zu | h2d %ld plan %ld arenas %ld bind %ld upload %ld launch %ld us\n",
+                     n_chunks, p.pages.size(), p.jobs.size(), p.snap.wins.size(), us(0, 1), us(1, 2), us(2, 3), us(3, 4),
                      us(4, 5), us(5, 6));
     }
     ctx->pending = true;
@@ -1582,8 +972,8 @@ int pf_wait(pf_ctx* ctx) {
         uint64_t need = 0;
         bool overflow = false;
         for (int c = 0; c < ctx->n_chunks; c++) {
-            if (ctx->chunks[c].ptype == PF_BYTE_ARRAY) need += align_up(uint64_t(std::max<int64_t>(r[c].num_chars, 0)), 256);
-            if (r[c].status == PF_ERR_CAPACITY && ctx->chunks[c].ptype == PF_BYTE_ARRAY && r[c].num_chars <= 0x7fffffff)
+            if (ctx->plan.chunks[c].ptype == PF_BYTE_ARRAY) need += align_up(uint64_t(std::max<int64_t>(r[c].num_chars, 0)), 256);
+            if (r[c].status == PF_ERR_CAPACITY && ctx->plan.chunks[c].ptype == PF_BYTE_ARRAY && r[c].num_chars <= 0x7fffffff)
                 overflow = true;
         }
         if (overflow && ctx->reruns == 0) {
@@ -1599,7 +989,7 @@ int pf_wait(pf_ctx* ctx) {
         int first_err = PF_OK;
         for (int c = 0; c < ctx->n_chunks; c++) {
             pf_column_info& ci = ctx->info[c];
-            const DevChunk& ck = ctx->chunks[c];
+            const DevChunk& ck = ctx->plan.chunks[c];
             ci.num_entries = ck.num_entries;
             ci.num_slots = r[c].num_slots;
             ci.num_values = r[c].num_values;
@@ -1710,9 +1100,9 @@ namespace {
 struct BatchLayout { size_t out, bits_off, bits, chars_off, chars, total; };
 BatchLayout batch_layout(const pf_ctx* ctx) {
     BatchLayout b{};
-    b.out = ctx->out_bytes;
+    b.out = ctx->plan.out_bytes;
     b.bits_off = align_up(b.out, 256);
-    b.bits = ctx->bits_bytes;
+    b.bits = ctx->plan.bits_bytes;
     b.chars_off = align_up(b.bits_off + b.bits, 256);
     const uint8_t* c0 = static_cast<const uint8_t*>(ctx->d_chars.p);
     size_t hi = 0, bound = 0;
@@ -1855,32 +1245,34 @@ int pf_snappy_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst
     job.dst = static_cast<uint8_t*>(ctx->d_scratch.p);
     job.src_len = uint32_t(n);
     job.dst_len = uint32_t(ulen);
-    ctx->jobs.assign(1, job);
-    ctx->chunks.clear();
-    ctx->pages.clear();
-    int rc = plan_snappy(ctx);
-    if (rc) return rc;
+    std::vector<SnappyJob> jobs(1, job);
+    SnappyPlan sp;
+    plan_snappy(jobs, sp);
+    HIPCHK(ctx, ctx->d_tokmap.ensure(sp.tokmap_bytes));
+    bind_snappy(jobs, sp, reinterpret_cast<uintptr_t>(ctx->d_tokmap.p));
+    ctx->d_last_win = sp.d_win;
+    ctx->d_last_lane_out = sp.d_lane_out;
     size_t m = 0;
     auto take = [](size_t& cursor, size_t sz) { size_t o = align_up(cursor, 256); cursor = o + sz; return o; };
-    size_t o_job = take(m, sizeof(SnappyJob)), o_pc = take(m, sizeof(int2) * ctx->pieces.size());
-    size_t o_sp = take(m, 4 * ctx->pieces.size()), o_fb = take(m, 4), o_wn = take(m, sizeof(int2) * ctx->wins.size());
+    size_t o_job = take(m, sizeof(SnappyJob)), o_pc = take(m, sizeof(int2) * sp.pieces.size());
+    size_t o_sp = take(m, 4 * sp.pieces.size()), o_fb = take(m, 4), o_wn = take(m, sizeof(int2) * sp.wins.size());
     size_t o_res = take(m, sizeof(DevChunkResult));
     m = align_up(m, 256);
     HIPCHK(ctx, ctx->d_meta.ensure(m));
     HIPCHK(ctx, ctx->h_meta.ensure(m));
     uint8_t* h = static_cast<uint8_t*>(ctx->h_meta.p);
     std::memset(h, 0, m);
-    std::memcpy(h + o_job, ctx->jobs.data(), sizeof(SnappyJob));
-    std::memcpy(h + o_pc, ctx->pieces.data(), sizeof(int2) * ctx->pieces.size());
-    std::memset(h + o_sp, 0xff, 4 * ctx->pieces.size());
-    std::memcpy(h + o_wn, ctx->wins.data(), sizeof(int2) * ctx->wins.size());
+    std::memcpy(h + o_job, jobs.data(), sizeof(SnappyJob));
+    std::memcpy(h + o_pc, sp.pieces.data(), sizeof(int2) * sp.pieces.size());
+    std::memset(h + o_sp, 0xff, 4 * sp.pieces.size());
+    std::memcpy(h + o_wn, sp.wins.data(), sizeof(int2) * sp.wins.size());
     uint8_t* d = static_cast<uint8_t*>(ctx->d_meta.p);
     HIPCHK(ctx, hipMemcpyAsync(d, h, m, hipMemcpyHostToDevice, st));
     ctx->d_last_splits = reinterpret_cast<const uint32_t*>(d + o_sp);
     launch_snappy(reinterpret_cast<const SnappyJob*>(d + o_job), 1, reinterpret_cast<const int2*>(d + o_wn),
-                  int(ctx->wins.size()), ctx->d_win, ctx->d_ent, ctx->d_lane_out, reinterpret_cast<const int2*>(d + o_pc),
-                  int(ctx->pieces.size()), reinterpret_cast<uint32_t*>(d + o_sp), reinterpret_cast<int*>(d + o_fb),
-                  reinterpret_cast<DevChunkResult*>(d + o_res), int(ctx->jobs.empty() ? 1 : ctx->jobs[0].n_win),
+                  int(sp.wins.size()), sp.d_win, sp.d_ent, sp.d_lane_out, reinterpret_cast<const int2*>(d + o_pc),
+                  int(sp.pieces.size()), reinterpret_cast<uint32_t*>(d + o_sp), reinterpret_cast<int*>(d + o_fb),
+                  reinterpret_cast<DevChunkResult*>(d + o_res), int(jobs[0].n_win),
                   ctx->opts.exec, st);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, ctx->h_res.ensure(512));
@@ -1990,8 +1382,8 @@ int pf_debug_snappy_tables(pf_ctx* ctx, uint32_t* splits, int n_splits, uint32_t
     if (!ctx || !ctx->d_last_splits) return fail(ctx, PF_ERR_STATE, "no snappy tables");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (splits) HIPCHK(ctx, hipMemcpy(splits, ctx->d_last_splits, 4 * size_t(n_splits), hipMemcpyDeviceToHost));
-    if (wins) HIPCHK(ctx, hipMemcpy(wins, ctx->d_win, sizeof(SnapWin) * size_t(n_wins), hipMemcpyDeviceToHost));
-    if (lane_out) HIPCHK(ctx, hipMemcpy(lane_out, ctx->d_lane_out, 256 * size_t(n_wins), hipMemcpyDeviceToHost));
+    if (wins) HIPCHK(ctx, hipMemcpy(wins, ctx->d_last_win, sizeof(SnapWin) * size_t(n_wins), hipMemcpyDeviceToHost));
+    if (lane_out) HIPCHK(ctx, hipMemcpy(lane_out, ctx->d_last_lane_out, 256 * size_t(n_wins), hipMemcpyDeviceToHost));
     if (tokmap) HIPCHK(ctx, hipMemcpy(tokmap, ctx->d_tokmap.p, 1024 * size_t(n_wins), hipMemcpyDeviceToHost));
     return PF_OK;
 }
@@ -2002,14 +1394,14 @@ int pf_debug_snappy_fallback(pf_ctx* ctx, int* out, int n_jobs) {
     if (!ctx || !ctx->d_meta.p || !ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int nj = int(ctx->jobs.size());
+    const int nj = int(ctx->plan.jobs.size());
     const int m = n_jobs < nj ? n_jobs : nj;
     if (out && m > 0) {
         std::vector<int> fb(size_t(m), 0);
-        HIPCHK(ctx, hipMemcpy(fb.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_fallback, 4 * size_t(m),
+        HIPCHK(ctx, hipMemcpy(fb.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->plan.off_fallback, 4 * size_t(m),
                               hipMemcpyDeviceToHost));
         for (int i = 0; i < m; i++) {
-            const SnappyJob& jb = ctx->jobs[size_t(i)];
+            const SnappyJob& jb = ctx->plan.jobs[size_t(i)];
             const int rec[5] = {fb[size_t(i)], int(jb.src_len), int(jb.dst_len), jb.chunk, jb.page};
             for (int q = 0; q < 5; q++) out[5 * i + q] = rec[q];
         }
@@ -2017,18 +1409,29 @@ int pf_debug_snappy_fallback(pf_ctx* ctx, int* out, int n_jobs) {
     return nj;
 }
 
-// Diagnostics (not part of pfloor.h): per page of the last finished pf_decode_row_group, what
-// k_snappy_head decided (DIRECT_NONE / DIRECT_VALUES / DIRECT_INPLACE). Returns the page count.
-int pf_debug_page_direct(pf_ctx* ctx, int* out, int n_pages) {
+namespace {
+// The first n_pages DevPage records of the last finished pf_decode_row_group as the device left
+// them. Returns the batch's page count, or a negative pf_status.
+int fetch_pages(pf_ctx* ctx, int n_pages, std::vector<DevPage>& pg) {
     if (!ctx || !ctx->d_meta.p || !ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int np = int(ctx->pages.size());
-    const int m = n_pages < np ? n_pages : np;
-    if (out && m > 0) {
-        std::vector<DevPage> pg(static_cast<size_t>(m));
-        HIPCHK(ctx, hipMemcpy(pg.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_pages, sizeof(DevPage) * size_t(m),
+    const int np = int(ctx->plan.pages.size());
+    pg.resize(size_t(std::max(0, std::min(n_pages, np))));
+    if (!pg.empty())
+        HIPCHK(ctx, hipMemcpy(pg.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->plan.off_pages, sizeof(DevPage) * pg.size(),
                               hipMemcpyDeviceToHost));
+    return np;
+}
+}  // namespace
+
+// Diagnostics (not part of pfloor.h): per page of the last finished pf_decode_row_group, what
+// k_snappy_head decided (DIRECT_NONE / DIRECT_VALUES / DIRECT_INPLACE). Returns the page count.
+int pf_debug_page_direct(pf_ctx* ctx, int* out, int n_pages) {
+    std::vector<DevPage> pg;
+    const int np = fetch_pages(ctx, out ? n_pages : 0, pg);
+    if (np >= 0) {
+        const int m = int(pg.size());
         for (int i = 0; i < m; i++) out[i] = pg[size_t(i)].direct;
     }
     return np;
@@ -2039,15 +1442,10 @@ int pf_debug_page_direct(pf_ctx* ctx, int* out, int n_pages) {
 // k_delta), seg_ok (1 = nested segment kernels, 2 = hand-over failed, decoded whole)}. Returns the
 // page count; out holds 3 ints per page.
 int pf_debug_page_paths(pf_ctx* ctx, int* out, int n_pages) {
-    if (!ctx || !ctx->d_meta.p || !ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int np = int(ctx->pages.size());
-    const int m = n_pages < np ? n_pages : np;
-    if (out && m > 0) {
-        std::vector<DevPage> pg(static_cast<size_t>(m));
-        HIPCHK(ctx, hipMemcpy(pg.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_pages, sizeof(DevPage) * size_t(m),
-                              hipMemcpyDeviceToHost));
+    std::vector<DevPage> pg;
+    const int np = fetch_pages(ctx, out ? n_pages : 0, pg);
+    if (np >= 0) {
+        const int m = int(pg.size());
         for (int i = 0; i < m; i++) {
             out[3 * i] = pg[size_t(i)].direct;
             out[3 * i + 1] = pg[size_t(i)].dbp_ok;
@@ -2061,15 +1459,10 @@ int pf_debug_page_paths(pf_ctx* ctx, int* out, int n_pages) {
 // DONE_NULL 4: which kernel took the page; k_page_null and k_flat_null both set DONE_NULL, and only
 // k_page_null's pages keep no level table (lvl = 0 in out[2 * i + 1])).
 extern "C" int pf_debug_page_done(pf_ctx* ctx, int* out, int n_pages) {
-    if (!ctx || !ctx->d_meta.p || !ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int np = int(ctx->pages.size());
-    const int m = n_pages < np ? n_pages : np;
-    if (out && m > 0) {
-        std::vector<DevPage> pg(static_cast<size_t>(m));
-        HIPCHK(ctx, hipMemcpy(pg.data(), static_cast<uint8_t*>(ctx->d_meta.p) + ctx->off_pages, sizeof(DevPage) * size_t(m),
-                              hipMemcpyDeviceToHost));
+    std::vector<DevPage> pg;
+    const int np = fetch_pages(ctx, out ? n_pages : 0, pg);
+    if (np >= 0) {
+        const int m = int(pg.size());
         for (int i = 0; i < m; i++) {
             out[2 * i] = pg[size_t(i)].done;
             uint32_t lt1 = 0;   // k_lvl's "block table fits" word (k_flat_null ran on the page)

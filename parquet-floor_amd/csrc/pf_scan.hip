@@ -22,6 +22,7 @@
 
 #include "pf_device.h"
 #include "pf_internal.h"
+#include "pf_launch.h"
 #include "pfloor.h"
 
 namespace pf {

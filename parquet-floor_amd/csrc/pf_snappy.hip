@@ -24,6 +24,7 @@
 // a launch that needs a large LDS allocation waits for CUs the other contexts' kernels occupy.
 #include <hip/hip_runtime.h>
 
+#include "pf_launch.h"
 #include "pf_snappy_par.h"
 
 namespace pf {

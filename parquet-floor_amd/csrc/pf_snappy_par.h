@@ -11,12 +11,9 @@
 namespace pf {
 
 
-constexpr uint32_t SNAP_RB = 128;                 // input bytes per lane region (index pass)
-constexpr uint32_t SNAP_WIN = 64 * SNAP_RB;       // 8 KiB of input per index window
+// (SNAP_RB, SNAP_WIN, SNAP_WWORDS, SNAP_BLOCK, SnapWin, SnapEnt: pf_internal.h, shared with the host planner)
 constexpr uint32_t SNAP_WSTAGE = SNAP_WIN + 96;   // staged window: + alignment shift (< 16) + 64-lane lookahead
-constexpr uint32_t SNAP_WWORDS = SNAP_WIN / 32;   // token-start bitmap words per window
 constexpr uint32_t SNAP_INVALID = 0xffffffffu;
-constexpr uint32_t SNAP_BLOCK = 65536;            // Google Snappy block = executor piece
 
 // per-job decode path (SnappyJob fallback flags, ordered: atomicMax escalates)
 // FB_INPLACE: the page needs no decompression (one literal, k_snappy_head); FB_LITCOPY: a page whose
@@ -28,20 +25,6 @@ enum : int { FB_OK = 0, FB_WHOLE = 1, FB_REDO = 2, FB_SERIAL = 3, FB_INPLACE = 4
 enum : uint32_t { WIN_BROKEN = 1, WIN_PASS = 2, WIN_NOCONV = 4 };
 // SnapWin.flags after the chain pass: how the window's bitmap relates to the true chain
 enum : uint32_t { WM_KEEP = 16, WM_SKIP = 17, WM_MERGE = 18, WM_FULL = 19, WM_DONE = 20 };
-
-// Result of the index pass for one 8 KiB input window.
-struct SnapWin {
-    uint32_t entry;   // chain start the window's bitmap was built from
-    uint32_t exit;    // first chain position at/after the window end (or the stream end)
-    uint32_t out;     // output bytes of the tokens in the window (on that chain)
-    uint32_t flags;
-};
-
-// Entry-table record (pos carries a 2-bit flag in its top bits).
-struct SnapEnt {
-    uint32_t pos;
-    uint32_t out;
-};
 
 struct SnapTok {
     uint64_t tl;      // input bytes (tag + operands + literal data); 64-bit: garbage lengths

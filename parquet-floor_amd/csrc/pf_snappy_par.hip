@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 
+#include "pf_launch.h"
 #include "pf_snappy_par.h"
 
 namespace pf {
@@ -2073,8 +2074,6 @@ extern "C" int pf_debug_stamps(unsigned long long* out, int n, int reset) {
     return 0;
 }
 #endif
-
-void launch_snappy_serial(const SnappyJob*, int, const int*, DevChunkResult*, hipStream_t);
 
 // Parse stage (token-start bitmaps, chain, 64 KiB split points) and execute stage, separately so
 // the runtime can time them apart.
