@@ -463,6 +463,10 @@ __global__ __launch_bounds__(DNT) void k_delta(const DevChunk* __restrict__ chun
 // against T and dx_bad and takes the page's chars from cpos. k_decode writes offsets and, for DLBA,
 // the chars; k_dba_chars materialises DELTA_BYTE_ARRAY values (prefix of the previous value +
 // suffix) in value order.
+// FIXED_LEN_BYTE_ARRAY pages in DELTA_BYTE_ARRAY (parquet-mr's v2 writer after a dictionary fallback)
+// take the same kernels: k_dlen also marks a value whose prefix + suffix is not type_length as bad,
+// decode_page (k_decode) checks the page's present values against T and dx_bad and leaves value k's
+// slot in aux[k], and k_dba_chars writes value k at values + aux[k] * type_length.
 constexpr uint64_t CPOS_BAD = 1ull << 62;
 
 __global__ __launch_bounds__(DNT) void k_dlen(const DevChunk* __restrict__ chunks, DevPage* pages, const int* page_list,
@@ -501,6 +505,7 @@ __global__ __launch_bounds__(DNT) void k_dlen(const DevChunk* __restrict__ chunk
         const uint32_t a = in ? uint32_t(la[k]) : 0u, b = in && dba ? uint32_t(lb[k]) : 0u;
         bool bad = in && (int32_t(a) < 0 || int32_t(b) < 0);
         const uint64_t len = uint64_t(a) + uint64_t(b);
+        if (in && ck.ptype == 7 && len != uint64_t(ck.width)) bad = true;   // FIXED_LEN_BYTE_ARRAY: every value type_length long
         const uint64_t sfx = dba ? b : a;           // bytes this value takes from the data section
         // inclusive scans (wave, then across waves)
         const int lane = tid & 63, wid = tid >> 6;
@@ -551,7 +556,8 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
     const DevPage& pg = pages[pi];
     const DevChunk& ck = chunks[pg.chunk];
     const int lane = threadIdx.x;
-    if (res[pg.chunk].status != 0 || !ck.chars || !pg.dx) return;
+    const bool flba = ck.ptype == 7;   // values + aux[k] * width (the slots decode_page left) instead of chars + cpos[k]
+    if (res[pg.chunk].status != 0 || !pg.dx || (flba ? (!ck.values || !pg.aux) : !ck.chars)) return;
     const uint8_t* p;
     uint64_t n;
     if (!values_section(pg, ck, p, n)) return;   // k_dlen reported it
@@ -562,7 +568,9 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
     const uint64_t* lb = la + cap;
     const uint8_t* sfx = p + pg.dx_data;
     const uint64_t sfx_n = n - pg.dx_data;
-    uint8_t* out = ck.chars + pg.char_start;
+    const uint64_t w = flba ? uint64_t(ck.width) : 0;
+    uint8_t* out = flba ? ck.values : ck.chars + pg.char_start;
+    const uint8_t* pv = out;    // previous value's bytes in the output
     uint64_t sp = 0;            // suffix stream position
     uint64_t ws = 0, we = 0;    // staged window [ws, we)
     int cur = 0;
@@ -570,7 +578,7 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
     for (uint64_t k = 0; k < nv; k++) {
         const uint32_t pl = uint32_t(la[k]), sl = uint32_t(lb[k]);
         const uint32_t len = pl + sl;
-        uint8_t* o = out + cpos[k];
+        uint8_t* o = flba ? out + uint64_t(pg.aux[k]) * w : out + cpos[k];
         const bool fits = len <= XV_CAP && plen <= XV_CAP;
         if (sl > 0 && (sp < ws || sp + sl > we)) {   // restage the suffix window at sp
             if (sl <= XS_WIN) {
@@ -586,7 +594,7 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
         uint8_t* keep = vbuf[cur];
         for (uint32_t j = uint32_t(lane); j < len; j += 64) {
             uint8_t b;
-            if (j < pl) b = fits ? prev[j] : out[cpos[k - 1] + j];
+            if (j < pl) b = fits ? prev[j] : pv[j];
             else b = staged ? sw[sp - ws + (j - pl)] : sfx[sp + (j - pl)];
             o[j] = b;
             if (len <= XV_CAP) keep[j] = b;
@@ -594,6 +602,7 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
         __syncthreads();
         sp += sl;
         plen = len;
+        pv = o;
         cur ^= 1;
     }
 }

@@ -1211,6 +1211,9 @@ __device__ __forceinline__ void decode_page(const DevChunk* __restrict__ chunks,
     const bool boolean = ck.ptype == 0;
     const int w = ck.width;
     const bool counted = ck.needs_count != 0;
+    // FIXED_LEN_BYTE_ARRAY in DELTA_BYTE_ARRAY: this pass writes validity and null slots and leaves each
+    // present value's slot in aux; k_dba_chars then builds the values in value order at their slots
+    const bool flba_dba = enc == 7 && ck.ptype == 7;
     // value-stream setup
     int id_bw = 0;
     if (dict) {
@@ -1233,7 +1236,7 @@ __device__ __forceinline__ void decode_page(const DevChunk* __restrict__ chunks,
     else if (enc == 3) supported = boolean;
     else if (enc == 5) supported = (ck.ptype == 1 || ck.ptype == 2) && pg.aux != nullptr;
     else if (enc == 9) supported = (ck.ptype == 4 || ck.ptype == 5);
-    else if (enc == 6 || enc == 7) supported = binary && pg.dx != nullptr;   // k_dlen lengths
+    else if (enc == 6 || enc == 7) supported = (binary || (flba_dba && pg.aux != nullptr)) && pg.dx != nullptr;   // k_dlen lengths
     if (!supported) { if (tid == 0) set_status(res, pg.chunk, dict ? ST_CORRUPT : ST_ENCODING, pi); return; }
     if (dict && id_bw > 32) { if (tid == 0) set_status(res, pg.chunk, ST_CORRUPT, pi); return; }
     if (binary && !ck.chars) return;   // capacity error already recorded by k_scan
@@ -1401,6 +1404,9 @@ __device__ __forceinline__ void decode_page(const DevChunk* __restrict__ chunks,
                     } else if (enc == 9) {
                         if (gv >= bss_total) S.verr = 1;
                         else for (int b = 0; b < w; b++) dst[b] = s.val[uint64_t(b) * bss_total + gv];
+                    } else if (flba_dba) {
+                        if (gv < uint64_t(pg.aux_cap)) pg.aux[gv] = uint32_t(slot);
+                        else S.verr = 1;
                     }
                 } else {
                     zero_value(ck.values + slot * uint64_t(w), w);
@@ -1420,6 +1426,10 @@ __device__ __forceinline__ void decode_page(const DevChunk* __restrict__ chunks,
         __syncthreads();
     }
     if (L.err || S.verr) { if (tid == 0) set_status(res, pg.chunk, ST_CORRUPT, pi); return; }
+    if (flba_dba) {   // the page's present values against k_dlen's streams and checks (as count_page does for BYTE_ARRAY)
+        if (int64_t(vidx) > pg.dx_total || int64_t(vidx) > pg.dx_bad) { if (tid == 0) set_status(res, pg.chunk, ST_CORRUPT, pi); return; }
+        if (tid == 0) pg.n_values = int64_t(vidx);   // k_dba_chars' value count (flat pages are not counted)
+    }
     if (!counted && tid == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&res[pg.chunk].num_values),
                                         (unsigned long long)vidx);
 }

@@ -163,8 +163,12 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                 pg.entry_start = entries;
                 entries += pd.num_values;
                 ck.n_pages++;
+                // FIXED_LEN_BYTE_ARRAY in DELTA_BYTE_ARRAY (parquet-mr's v2 writer after a dictionary fallback)
+                const bool flba_dba = cd.physical_type == PF_FIXED_LEN_BYTE_ARRAY && pd.encoding == PF_ENC_DELTA_BYTE_ARRAY;
                 if (cd.physical_type == PF_BYTE_ARRAY)   // value positions / ids + per-block chars (k_flat)
                     pp.aux_off = take(scratch, 4ull * pd.num_values + 16 + 8ull * (uint64_t(pd.num_values) / FBLK + 2), 256);
+                else if (flba_dba)   // slot of every present value (decode_page -> k_dba_chars)
+                    pp.aux_off = take(scratch, 4ull * pd.num_values + 16, 256);
                 else if (pd.encoding == PF_ENC_DELTA_BINARY_PACKED && int_type(cd.physical_type)) {
                     pp.aux_off = take(scratch, 8ull * pd.num_values + 8, 256);
                     // block-parallel decode (k_dbp_*); PF_DBP_PAR=0: every page on the one-workgroup k_delta (tests)
@@ -178,8 +182,8 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                 }
                 if (pp.aux_off != NO_OFF) pg.aux_cap = pg.num_values;
                 if (cd.physical_type == PF_BYTE_ARRAY) p.chars_hint += pd.uncompressed_size;
-                if (cd.physical_type == PF_BYTE_ARRAY &&
-                    (pd.encoding == PF_ENC_DELTA_LENGTH_BYTE_ARRAY || pd.encoding == PF_ENC_DELTA_BYTE_ARRAY))
+                if (flba_dba || (cd.physical_type == PF_BYTE_ARRAY &&
+                                 (pd.encoding == PF_ENC_DELTA_LENGTH_BYTE_ARRAY || pd.encoding == PF_ENC_DELTA_BYTE_ARRAY)))
                     pp.dx_off = take(scratch, 8ull * (3ull * uint64_t(pd.num_values) + 1), 256);   // k_dlen
                 if (cd.max_rep == 0 && cd.physical_type != PF_BOOLEAN && dict_encoded(pd.encoding))
                     pp.rt_off = take(scratch, RT_BYTES, 256);   // k_runs table

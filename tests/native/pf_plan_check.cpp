@@ -81,7 +81,8 @@ void check_arenas(const BatchPlan& p, size_t n_bytes) {
         check((pg.lvl != nullptr) == bool(pg.flags & PG_V2) && (!pg.lvl || addr(pg.lvl) == BASES.in + pp.in_off), "page %ld lvl", I);
         if (pp.aux_off != NO_OFF) {
             const uint64_t len = (pg.flags & PG_DICT) ? 8 * (nv + 1)
-                                 : ck.ptype == PF_BYTE_ARRAY ? 4 * nv + 16 + 8 * (nv / FBLK + 2) : 8 * nv + 8;
+                                 : ck.ptype == PF_BYTE_ARRAY ? 4 * nv + 16 + 8 * (nv / FBLK + 2)
+                                 : ck.ptype == PF_FIXED_LEN_BYTE_ARRAY ? 4 * nv + 16 : 8 * nv + 8;   // (FLBA: DELTA_BYTE_ARRAY slot map)
             S.push_back({pp.aux_off, len, 256, "aux", I});
             check(pg.aux_cap == int64_t(nv), "page %ld aux_cap", I);
         }
@@ -501,6 +502,20 @@ void hand_made() {
             run(name, {c}, o, p);
             check((p.pages[0].dbp != nullptr) == (nv >= 16384 && par) && p.lists[L_DELTA].size() == 1 && p.pages[0].aux != nullptr, "dbp tables");
             check((p.max_dbp_nwin > 0) == (nv >= 16384 && par), "max_dbp_nwin %d", p.max_dbp_nwin);
+        }
+    // 4b. DELTA_BYTE_ARRAY: BYTE_ARRAY and FIXED_LEN_BYTE_ARRAY pages get k_dlen's tables (FLBA also a slot map) and
+    // k_dba_chars; no other type does (k_decode reports the page)
+    for (int pt : {PF_BYTE_ARRAY, PF_FIXED_LEN_BYTE_ARRAY, PF_INT32})
+        for (int rep : {0, 1}) {
+            Chunk c = chunk(pt, 1 + rep, rep, PF_CODEC_UNCOMPRESSED);
+            c.d.type_length = pt == PF_FIXED_LEN_BYTE_ARRAY ? 7 : 0;
+            c.pages.push_back(page(PF_PAGE_DATA, PF_ENC_DELTA_BYTE_ARRAY, 5000, 30000, 30000));
+            std::snprintf(name, sizeof name, "4b delta byte array type %d rep %d", pt, rep);
+            run(name, {c}, PfOpts{}, p);
+            const bool tabs = pt != PF_INT32;
+            check((p.pages[0].dx != nullptr) == tabs && (p.pages[0].aux != nullptr) == tabs && p.lists[L_DLEN].size() == size_t(tabs) &&
+                      p.lists[L_DBA].size() == size_t(tabs), "delta byte array tables");
+            check(p.n_decode_first == 1 && p.pages[0].nseg == 0, "delta byte array routing");
         }
     // 5. BYTE_ARRAY dictionary at and above the sticky threshold
     for (uint32_t db : {65536u, 65537u}) {

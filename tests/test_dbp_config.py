@@ -14,58 +14,7 @@ import numpy as np
 import pytest
 
 
-def _uvarint(v):
-    out = bytearray()
-    while True:
-        b = v & 0x7F
-        v >>= 7
-        if v:
-            out.append(b | 0x80)
-        else:
-            out.append(b)
-            return bytes(out)
-
-
-def _zz(v):
-    return (v << 1) ^ (v >> 63)
-
-
-def _wrap(v, bits):
-    v &= (1 << bits) - 1
-    return v - (1 << bits) if v >> (bits - 1) else v
-
-
-def _dbp(values, block, nmini, junk_tail=False, bad_block=None, bits=64):
-    """parquet-mr's DeltaBinaryPackingValuesWriter[ForLong] layout; bits=32 is the INT32 writer:
-    deltas and (delta - min_delta) wrap mod 2^32, as its int arithmetic does."""
-    vpm = block // nmini
-    out = bytearray(_uvarint(block) + _uvarint(nmini) + _uvarint(len(values)) + _uvarint(_zz(int(values[0])) & (2**64 - 1)))
-    deltas = [_wrap(int(values[i]) - int(values[i - 1]), bits) for i in range(1, len(values))]
-    for b0 in range(0, len(deltas), block):
-        d = deltas[b0:b0 + block]
-        mn = min(d)
-        out += _uvarint(_zz(mn) & (2**64 - 1))
-        rel = [(x - mn) & ((1 << bits) - 1) for x in d]
-        widths, data = [], bytearray()
-        for m in range(nmini):
-            chunk = rel[m * vpm:(m + 1) * vpm]
-            w = max((x.bit_length() for x in chunk), default=0)
-            if not chunk:
-                widths.append(200 if junk_tail else 0)   # unconsumed miniblock: its width is never checked
-                continue
-            if bad_block is not None and b0 // block == bad_block and m == 0:
-                w = bits + 1                                # a width no reader of this type accepts
-            widths.append(w)
-            if w > bits:
-                data += bytes((vpm * 64 + 7) // 8)
-                continue
-            chunk = chunk + [0] * (vpm - len(chunk))
-            acc = 0
-            for i, x in enumerate(chunk):
-                acc |= x << (i * w)
-            data += acc.to_bytes((vpm * w + 7) // 8, "little")
-        out += bytes(widths) + data
-    return bytes(out)
+from pagekit import _dbp, _uvarint   # (the DELTA_BINARY_PACKED writer lives in the page assembler now)
 
 
 def _ci32(fid_delta, v):   # compact i32 field: header (delta << 4 | 5) + zigzag varint

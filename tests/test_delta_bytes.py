@@ -1,7 +1,8 @@
 """DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY pages — the string encodings parquet-mr's PARQUET_2_0
 writer falls back to (bsp/ParquetWriter.java:66). Files are written here by
 pyarrow (an independent implementation): multi-page chunks, v1 and v2 pages, nulls, empty strings,
-values longer than k_dba_chars' LDS buffers, and LIST<STRING> leaves. The CPU test pins the oracle
+values longer than k_dba_chars' LDS buffers, a FIXED_LEN_BYTE_ARRAY(7) column in DELTA_BYTE_ARRAY,
+and LIST<STRING> leaves. The CPU test pins the oracle
 to pyarrow's reading of the files; the GPU test compares the HIP path (through the C ABI) with the
 oracle bit-exactly."""
 import importlib.util
@@ -13,7 +14,7 @@ import pytest
 from conftest import GOLDEN
 from golden_util import assert_chunk_equal
 
-ENC = {"dlba": "DELTA_LENGTH_BYTE_ARRAY", "dba": "DELTA_BYTE_ARRAY", "dba_long": "DELTA_BYTE_ARRAY",
+ENC = {"dlba": "DELTA_LENGTH_BYTE_ARRAY", "dba": "DELTA_BYTE_ARRAY", "dba_long": "DELTA_BYTE_ARRAY", "fdba": "DELTA_BYTE_ARRAY",
        "l.list.element": "DELTA_LENGTH_BYTE_ARRAY", "ldba.list.element": "DELTA_BYTE_ARRAY"}
 CASES = [("1.0", "none"), ("1.0", "snappy"), ("2.0", "snappy")]
 
@@ -46,8 +47,11 @@ def _table(n, seed):
                                             for _ in range(int(rng.integers(0, 5)))] for _ in range(n)]
     ldba = [None if rng.random() < 0.1 else sorted(word(3) + word(int(rng.integers(0, 5)))
                                                    for _ in range(int(rng.integers(0, 4)))) for _ in range(n)]
+    # FIXED_LEN_BYTE_ARRAY(7) in DELTA_BYTE_ARRAY (parquet-mr's v2 writer after a dictionary fallback), with nulls
+    fdba = sorted((rng.integers(0, 3, 7) + 65).astype(np.uint8).tobytes() for _ in range(n))
+    fdba = [None if rng.random() < 0.1 else v for v in fdba]
     return pa.table({"dlba": pa.array(dlba, pa.string()), "dba": pa.array(dba, pa.string()),
-                     "dba_long": pa.array(longv, pa.string()),
+                     "dba_long": pa.array(longv, pa.string()), "fdba": pa.array(fdba, pa.binary(7)),
                      "l": pa.array(lst, pa.list_(pa.string())), "ldba": pa.array(ldba, pa.list_(pa.string()))})
 
 

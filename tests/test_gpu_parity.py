@@ -10,8 +10,9 @@ from golden_util import assert_chunk_equal, load_expected
 
 pytestmark = pytest.mark.gpu
 
-# Encodings the HIP path does not decode (none at present): chunks using them must fail loudly
-# with PF_ERR_UNSUPPORTED_ENCODING (-3), never return wrong data.
+# Encodings the HIP path does not decode: none (the last one, DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY,
+# is decoded by k_dlen + k_dba_chars; test_page_matrix.py, test_delta_bytes.py). A chunk using one would
+# have to fail loudly with PF_ERR_UNSUPPORTED_ENCODING (-3), never return wrong data.
 UNSUPPORTED = set()
 
 
@@ -178,10 +179,19 @@ def _big_file(tmp_path, rows, nulls):
     for k, v in cols.items():
         mask = (rng.random(rows) < 0.3) if nulls else None
         arrays[k] = pa.array(v, mask=mask)
+    # FIXED_LEN_BYTE_ARRAY(7) in DELTA_BYTE_ARRAY (sorted: shared prefixes), nulls as the other columns
+    fl = np.sort(rng.integers(0, 1 << 40, rows)).astype(">u8").view(np.uint8).reshape(-1, 8)[:, 1:]
+    arrays["fdba"] = pa.array([r.tobytes() for r in fl], pa.binary(7), mask=(rng.random(rows) < 0.3) if nulls else None)
     t = pa.table(arrays)
     path = str(tmp_path / f"big_{rows}_{int(nulls)}.parquet")
-    pq.write_table(t, path, compression="snappy", row_group_size=rows // 2,
-                   use_dictionary=["runs", "sdict", "key"], data_page_size=1 << 20)
+    # the file with nulls is a format-version 1.0 file: PLAIN_DICTIONARY on its dictionary and data pages
+    # (parquet-mr's default v1 writer), the other one RLE_DICTIONARY
+    pq.write_table(t, path, compression="snappy", row_group_size=rows // 2, version="1.0" if nulls else "2.6",
+                   use_dictionary=["runs", "sdict", "key"], column_encoding={"fdba": "DELTA_BYTE_ARRAY"},
+                   data_page_size=1 << 20)
+    md = pq.ParquetFile(path).metadata.row_group(0)
+    assert "DELTA_BYTE_ARRAY" in md.column(5).encodings
+    assert ("PLAIN_DICTIONARY" if nulls else "RLE_DICTIONARY") in md.column(1).encodings, md.column(1).encodings
     return path
 
 
