@@ -113,6 +113,24 @@ struct SnappyJob {
     uint32_t lit;         // FB_LITCOPY: the page's literal count (their table is in tokmap)
 };
 
+// One ZSTD decompression job (pf_zstd.hip): the frames of src -> dst.
+struct ZstdJob {
+    const uint8_t* src;
+    uint8_t* dst;
+    uint32_t src_len;
+    uint32_t dst_len;     // room at dst; exact = 1: what the frames have to produce (a page's body)
+    int32_t page;         // global page index (for error attribution)
+    int32_t chunk;
+    uint32_t exact;
+    uint32_t produced;    // out: bytes written (0 when the job failed)
+};
+constexpr int ZSTD_GRID = 512;                   // most workgroups of k_zstd: each owns a literal area
+constexpr uint32_t ZSTD_LIT_MAX = 128u << 10;    // literals of one block (Block_Maximum_Size)
+// Bytes of one workgroup's literal area when the largest job produces max_dst bytes.
+PF_HD inline uint32_t zstd_lit_stride(uint32_t max_dst) {
+    return ((max_dst < ZSTD_LIT_MAX ? max_dst : ZSTD_LIT_MAX) + 255u) / 256u * 256u + 256u;
+}
+
 // DONE_PAGE: k_page_null decoded the whole page (with DONE_NULL); k_lvl and k_flat_null skip only
 // such pages -- never DONE_NULL itself, which k_flat_null's own finished blocks of the page set.
 enum : int32_t { DONE_FIXED = 1, DONE_FLAT = 2, DONE_NULL = 4, DONE_PAGE = 8 };

@@ -18,6 +18,10 @@ void launch_snappy(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int 
                    uint32_t* d_lane_out, const int2* d_pieces, int n_pieces, uint32_t* d_splits, int* d_fb,
                    DevChunkResult* d_res, int max_nwin, int exec, hipStream_t s);
 
+// pf_zstd.hip
+void launch_zstd(ZstdJob* d_jobs, const int* d_order, int n_jobs, uint8_t* d_lit, uint32_t lit_stride, DevChunkResult* d_res,
+                 hipStream_t s);
+
 // pf_pages.hip
 void launch_snappy_head(SnappyJob* d_jobs, int n_jobs, DevPage* d_pages, const DevChunk* d_chunks, int* d_fb,
                         const DevChunkResult* d_res, hipStream_t st);

@@ -107,7 +107,8 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
     ck.first_page = int(p.pages.size());
     int64_t& hs = p.host_status[size_t(c)];
     if (ck.width < 0) hs = PF_ERR_UNSUPPORTED_TYPE;
-    else if (cd.codec != PF_CODEC_UNCOMPRESSED && cd.codec != PF_CODEC_SNAPPY) hs = PF_ERR_UNSUPPORTED_CODEC;
+    else if (cd.codec != PF_CODEC_UNCOMPRESSED && cd.codec != PF_CODEC_SNAPPY && cd.codec != PF_CODEC_ZSTD)
+        hs = PF_ERR_UNSUPPORTED_CODEC;
     else if (cd.max_def < 0 || cd.max_def > 255 || cd.max_rep < 0 || cd.max_rep > 255 || cd.n_pages < 0 ||
              (cd.n_pages > 0 && !cd.pages) || cd.chunk_offset + cd.chunk_size > n_bytes)
         hs = PF_ERR_INVALID_ARG;
@@ -135,17 +136,25 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
             if (v2 && (pd.rep_bytes < 0 || pd.def_bytes < 0 || lvl > pd.compressed_size || lvl > pd.uncompressed_size)) {
                 hs = PF_ERR_CORRUPT_PAGE; break;
             }
-            bool compressed = cd.codec == PF_CODEC_SNAPPY && (!v2 || pd.is_compressed);
+            bool compressed = cd.codec != PF_CODEC_UNCOMPRESSED && (!v2 || pd.is_compressed);
             PagePlan pp{cd.chunk_offset + pd.offset, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF};
             if (v2) { pg.rep_len = uint32_t(pd.rep_bytes); pg.def_len = uint32_t(pd.def_bytes); }
             if (compressed) {
                 pp.scratch_off = take(scratch, pd.uncompressed_size - lvl, 16);
                 pg.flags |= PG_COMPRESSED;
                 pg.body_len = pd.uncompressed_size - lvl;
-                SnappyJob j{};
-                j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
-                j.page = int(p.pages.size()); j.chunk = c;
-                p.jobs.push_back(j);
+                if (cd.codec == PF_CODEC_ZSTD) {
+                    ZstdJob j{};
+                    j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
+                    j.page = int(p.pages.size()); j.chunk = c;
+                    j.exact = 1;
+                    p.zjobs.push_back(j);
+                } else {
+                    SnappyJob j{};
+                    j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
+                    j.page = int(p.pages.size()); j.chunk = c;
+                    p.jobs.push_back(j);
+                }
             } else {
                 pg.body_len = pd.compressed_size - lvl;
             }
@@ -222,6 +231,7 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
     if (hs != 0) {   // drop this chunk's pages and jobs
         while (int(p.pages.size()) > ck.first_page) { p.pages.pop_back(); p.pplan.pop_back(); }
         while (!p.jobs.empty() && p.jobs.back().chunk == c) p.jobs.pop_back();
+        while (!p.zjobs.empty() && p.zjobs.back().chunk == c) p.zjobs.pop_back();
         ck.n_pages = 0; ck.dict_page = -1; entries = 0;
     }
     if (ck.dict_page >= 0) ck.first_page = ck.dict_page + 1;
@@ -416,6 +426,21 @@ void plan_routes(const PfOpts& opts, BatchPlan& p) {
     }
 }
 
+// ZSTD jobs: the dispatch order (the most compressed bytes first, so the longest pages do not start
+// last; ties in page order) and one literal area per resident workgroup of k_zstd.
+void plan_zstd(BatchPlan& p) {
+    std::vector<int>& order = p.lists[L_ZSTD];
+    uint32_t max_dst = 0;
+    for (size_t j = 0; j < p.zjobs.size(); j++) {
+        order.push_back(int(j));
+        max_dst = std::max(max_dst, p.zjobs[j].dst_len);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.zjobs[size_t(a)].src_len > p.zjobs[size_t(b)].src_len; });
+    p.zstd_grid = uint32_t(std::min<size_t>(p.zjobs.size(), size_t(ZSTD_GRID)));
+    p.zlit_stride = p.zstd_grid ? zstd_lit_stride(max_dst) : 0;
+    p.off_zlit = take(p.scratch_bytes, size_t(p.zstd_grid) * p.zlit_stride, 256);
+}
+
 void plan_meta(BatchPlan& p) {
     size_t m = 0;
     for (int l = 0; l < N_LISTS; l++) p.list_base[l + 1] = p.list_base[l] + p.lists[l].size();
@@ -431,6 +456,7 @@ void plan_meta(BatchPlan& p) {
     p.off_bajobs = take(m, sizeof(BaJob) * p.bajobs.size());
     p.off_batiles = take(m, sizeof(Int2) * p.ba_tiles.size());
     p.off_nfbq = take(m, 16 + sizeof(Int2) * size_t(p.n_flat_fixed + p.n_null4 + p.n_null8), 16);   // fallback queue
+    p.off_zjobs = take(m, sizeof(ZstdJob) * p.zjobs.size());
     p.meta_bytes = take(m, 256) + 256;   // arena counter lives in the last 256 bytes
 }
 
@@ -441,7 +467,7 @@ void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const Pf
     p.chunks.assign(size_t(n_chunks), DevChunk{});
     p.host_status.assign(size_t(n_chunks), 0);
     p.oplan.resize(size_t(n_chunks));
-    p.pages.clear(); p.pplan.clear(); p.jobs.clear();
+    p.pages.clear(); p.pplan.clear(); p.jobs.clear(); p.zjobs.clear();
     p.bajobs.clear(); p.ba_tiles.clear(); p.ba_bm.clear();
     for (auto& l : p.lists) l.clear();
     p.ba_short_dict = p.ba_short_data = true;
@@ -457,6 +483,7 @@ void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const Pf
     plan_page_tables(p);
     plan_routes(opts, p);
     plan_snappy(p.jobs, p.snap);
+    plan_zstd(p);
     plan_meta(p);
 }
 
@@ -496,6 +523,11 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
         pg.jfb = reinterpret_cast<const int*>(a.meta + p.off_fallback) + j;
     }
     bind_snappy(p.jobs, p.snap, a.tokmap);
+    for (ZstdJob& jb : p.zjobs) {
+        const DevPage& pg = p.pages[size_t(jb.page)];
+        jb.src = at(a.in, p.pplan[size_t(jb.page)].in_off) + pg.rep_len + pg.def_len;
+        jb.dst = at(S, p.pplan[size_t(jb.page)].scratch_off);
+    }
     for (size_t b = 0; b < p.bajobs.size(); b++) {
         BaJob& J = p.bajobs[b];
         const size_t nw = size_t(J.n_tiles) * (BA_TILE / 32);

@@ -5,7 +5,7 @@
 // planner (pf_plan.cpp, no HIP calls) turns the descriptors into flat DevChunk / DevPage /
 // SnappyJob tables, launch lists and arena sizes; this file grows the arenas to those sizes, has
 // the planner bind its offsets to them, uploads the tables in one copy, and enqueues
-//   k_snappy -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
+//   k_snappy / k_zstd -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
 // on the context stream. Nothing synchronises until pf_wait.
 #include <hip/hip_runtime.h>
 
@@ -255,6 +255,9 @@ int enqueue_kernels(pf_ctx* ctx) {
     EVREC(ctx, ctx->ev[2], st);
     if (!(skip & 2u))
         launch_snappy_exec(d_jobs, n_jobs, d_pieces, int(p.snap.pieces.size()), d_splits, d_fallback, d_res, ctx->opts.exec, st);
+    // ZSTD pages (a batch without one enqueues nothing here)
+    launch_zstd(reinterpret_cast<ZstdJob*>(meta + p.off_zjobs), list(L_ZSTD), int(p.zjobs.size()),
+                static_cast<uint8_t*>(ctx->d_scratch.p) + p.off_zlit, p.zlit_stride, d_res, st);
     EVREC(ctx, ctx->ev[3], st);
     BaJob* d_bajobs = reinterpret_cast<BaJob*>(meta + p.off_bajobs);
     const int2* d_batiles = reinterpret_cast<const int2*>(meta + p.off_batiles);
@@ -313,6 +316,7 @@ int upload_meta(pf_ctx* ctx) {
     put(p.off_chunks, p.chunks);
     put(p.off_pages, p.pages);
     put(p.off_jobs, p.jobs);
+    put(p.off_zjobs, p.zjobs);
     put(p.off_pieces, p.snap.pieces);
     std::memset(h + p.off_splits, 0xff, sizeof(uint32_t) * p.snap.n_splits);
     put(p.off_wins, p.snap.wins);
@@ -1282,6 +1286,53 @@ int pf_snappy_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst
     HIPCHK(ctx, hipStreamSynchronize(st));
     const DevChunkResult* r = static_cast<const DevChunkResult*>(ctx->h_res.p);
     if (r->status != 0) return fail(ctx, r->status, "snappy: corrupt input");
+    return PF_OK;
+}
+
+// One buffer of ZSTD frames through k_zstd (pf_zstd.hip), as one job with room for cap bytes.
+int pf_zstd_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len) {
+    if (!ctx || (!src && n) || (!dst && cap) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+    if (n > (1ull << 30) || cap > (1ull << 30)) return fail(ctx, PF_ERR_INVALID_ARG, "zstd: buffer too large");
+    *out_len = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // arenas may be reallocated below
+    ctx->copies_pending = false;
+    ctx->n_chunks = 0;
+    ctx->info.clear();
+    ctx->tables_from_decode = false;   // d_meta now holds this call's layout
+    const uint32_t stride = zstd_lit_stride(uint32_t(cap));
+    const size_t o_lit = align_up(cap + 16, 256);
+    HIPCHK(ctx, ctx->d_in.ensure(std::max<size_t>(n, 1)));
+    HIPCHK(ctx, ctx->d_scratch.ensure(o_lit + stride));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_in.p, src, n, hipMemcpyHostToDevice, st));
+    ZstdJob job{};
+    job.src = static_cast<const uint8_t*>(ctx->d_in.p);
+    job.dst = static_cast<uint8_t*>(ctx->d_scratch.p);
+    job.src_len = uint32_t(n);
+    job.dst_len = uint32_t(cap);
+    const size_t o_res = 256, m = 512;
+    HIPCHK(ctx, ctx->d_meta.ensure(m));
+    HIPCHK(ctx, ctx->h_meta.ensure(m));
+    HIPCHK(ctx, ctx->h_res.ensure(512));
+    uint8_t* h = static_cast<uint8_t*>(ctx->h_meta.p);
+    std::memset(h, 0, m);
+    std::memcpy(h, &job, sizeof job);
+    uint8_t* d = static_cast<uint8_t*>(ctx->d_meta.p);
+    HIPCHK(ctx, hipMemcpyAsync(d, h, m, hipMemcpyHostToDevice, st));
+    launch_zstd(reinterpret_cast<ZstdJob*>(d), nullptr, 1, static_cast<uint8_t*>(ctx->d_scratch.p) + o_lit, stride,
+                reinterpret_cast<DevChunkResult*>(d + o_res), st);
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t* hr = static_cast<uint8_t*>(ctx->h_res.p);
+    HIPCHK(ctx, hipMemcpyAsync(hr, d, m, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ZstdJob done;
+    std::memcpy(&done, hr, sizeof done);
+    const DevChunkResult* r = reinterpret_cast<const DevChunkResult*>(hr + o_res);
+    if (r->status != 0) return fail(ctx, r->status, "zstd: corrupt input");
+    if (done.produced) HIPCHK(ctx, hipMemcpy(dst, ctx->d_scratch.p, done.produced, hipMemcpyDeviceToHost));
+    *out_len = done.produced;
     return PF_OK;
 }
 

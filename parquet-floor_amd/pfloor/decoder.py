@@ -203,6 +203,18 @@ class GpuDecoder:
             return rc, None
         return dst[:out_len.value].tobytes(), L.pf_snappy_last_fallback(self.h)
 
+    def zstd_decompress(self, data: bytes, size: int):
+        """ZSTD frames -> bytes on the GPU (k_zstd). size: the uncompressed length, as a page header
+        states it. Returns the bytes, or a negative status: -2 when the frames are damaged or do not
+        produce exactly size bytes."""
+        src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+        out_len = C.c_size_t()
+        dst = np.zeros(max(1, size), dtype=np.uint8)
+        rc = lib().pf_zstd_decompress(self.h, src.ctypes.data, len(data), dst.ctypes.data, size, C.byref(out_len))
+        if rc != 0:
+            return rc
+        return dst[:size].tobytes() if out_len.value == size else -2
+
     def scan_pages(self, data, chunks, verify_crc=False, page_cap=4096):
         """GPU page-header scan (pf_scan_pages) of column chunks in one host buffer.
         chunks: [(chunk_offset, chunk_size, num_values)]. Returns (rc, [(status, err_page, crc_pages,
