@@ -187,7 +187,7 @@ __device__ bool dbp_decode_wg(DbpLds& S, const uint8_t* p, uint64_t n, bool is64
 // k_delta walks block headers on one lane (one dependent header read per block: ~250 us for a
 // 494 K-value page). Blocks hold `block` values each (the last one fewer), so block b's first value
 // is 1 + b * block: only the blocks' byte positions form a chain. k_dbp_pos finds them the way
-// k_nest_lvl finds level runs (pf_pages.hip): per DBP_WIN-byte window every position is decoded as
+// k_nest_lvl finds level runs (pf_decode.hip): per DBP_WIN-byte window every position is decoded as
 // a block header (next = position + header + sum of the miniblocks' bytes), pointer jumping gives
 // each position's window exit, windows hand over the true chain's entry in one pass, then walk their
 // part of it storing the positions. k_dbp_blk (one wave per block) sums each block's deltas,

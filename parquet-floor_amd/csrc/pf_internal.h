@@ -186,7 +186,7 @@ struct DevPage {
     const int* jfb;
     int32_t direct;
     int32_t direct_pad;
-    // nested data pages split into segments of seg_len entries (k_nest_*, pf_pages.hip), else null:
+    // nested data pages split into segments of seg_len entries (k_nest_*, pf_decode.hip), else null:
     // {RleState ck[3][nseg] (rep, def, value stream state at each segment's start), SegRec rec[nseg]}
     uint8_t* seg;
     int32_t nseg;
@@ -267,7 +267,7 @@ PF_HD inline uint32_t lvl_table_cap(int32_t num_values) {
 }
 
 // One PLAIN BYTE_ARRAY length walk (a BYTE_ARRAY dictionary page, or the values section of a
-// PLAIN BYTE_ARRAY data page), done tile-parallel by the k_ba_* kernels (pf_pages.hip).
+// PLAIN BYTE_ARRAY data page), done tile-parallel by the k_ba_* kernels (pf_ba.hip).
 // BA_RELINK: the fused tile pass (k_ba_tile) rejected the job -- a value longer than its halo, or
 // filters it could not separate -- and k_ba_fallback re-links it over the whole job before any walk
 enum : int32_t { BA_OK = 0, BA_FALLBACK = 1, BA_SKIP = 2, BA_RELINK = 3 };

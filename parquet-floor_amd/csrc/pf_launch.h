@@ -22,25 +22,33 @@ void launch_snappy(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int 
 void launch_zstd(ZstdJob* d_jobs, const int* d_order, int n_jobs, uint8_t* d_lit, uint32_t lit_stride, DevChunkResult* d_res,
                  hipStream_t s);
 
-// pf_pages.hip
+// pf_snappy_head.hip
 void launch_snappy_head(SnappyJob* d_jobs, int n_jobs, DevPage* d_pages, const DevChunk* d_chunks, int* d_fb,
                         const DevChunkResult* d_res, hipStream_t st);
 void launch_snappy_litcopy(const SnappyJob* d_jobs, const int* d_list, int n, const int* d_fb, hipStream_t st);
+
+// pf_ba.hip
 void launch_ba(BaJob* d_jobs, int n_jobs, const int2* d_tiles, int n_tiles, DevChunkResult* d_res, hipStream_t st,
                bool short_values);
+
+// pf_pages.hip
 void launch_runs(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
 void launch_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st,
                 bool page_null, NullCaps nc);
+void launch_count_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_flat, const int2* d_dblk,
+                       int n_dblk, DevChunkResult* d_res, BaJob* d_bajobs, hipStream_t st);
+void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
+                 DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
+
+// pf_decode.hip
 void launch_nest_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int max_nwin, DevChunkResult* d_res,
                      hipStream_t st, bool force_timeout);
-void launch_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_flat, const int2* d_dblk,
-                  int n_dblk, DevChunkResult* d_res, BaJob* d_bajobs, hipStream_t st, int idle_grid);
+void launch_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, BaJob* d_bajobs,
+                  hipStream_t st, int idle_grid);
 void launch_nest_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, const int2* d_segs, int n_segs,
                        DevChunkResult* d_res, hipStream_t st);
 void launch_scan(DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, uint8_t* arena,
                  uint64_t cap, unsigned long long* used, hipStream_t st);
-void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
-                 DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
 void launch_decode(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_first, DevChunkResult* d_res,
                    hipStream_t st, int idle_grid);
 void launch_nest_decode(const DevChunk* d_chunks, DevPage* d_pages, const int2* d_segs, int n_segs, DevChunkResult* d_res,

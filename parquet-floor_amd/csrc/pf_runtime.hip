@@ -247,7 +247,7 @@ int enqueue_kernels(pf_ctx* ctx) {
         if (p.npub_bytes) HIPCHK(ctx, hipMemsetAsync(static_cast<uint8_t*>(ctx->d_scratch.p) + p.off_npub, 0, p.npub_bytes, st));
     }
     EVREC(ctx, ctx->ev[1], st);
-    // single-literal pages in place, PLAIN fixed-width pages straight into the column (pf_pages.hip)
+    // single-literal pages in place, PLAIN fixed-width pages straight into the column (pf_snappy_head.hip)
     if (!(skip & 1u)) launch_snappy_head(d_jobs, n_jobs, d_pages, d_chunks, d_fallback, d_res, st);
     if (!(skip & 1u)) launch_snappy_litcopy(d_jobs, list(L_DJOBS), len(L_DJOBS), d_fallback, st);
     if (!(skip & 1u)) launch_snappy_parse(d_jobs, n_jobs, d_wins, int(p.snap.wins.size()), p.snap.d_win, p.snap.d_ent,
@@ -273,8 +273,11 @@ int enqueue_kernels(pf_ctx* ctx) {
     launch_dlen(d_chunks, d_pages, list(L_DLEN), len(L_DLEN), d_res, st);
     EVREC(ctx, ctx->ev[6], st);
     launch_nest_lvl(d_chunks, d_pages, list(L_NEST), n_nest, p.max_nwin, d_res, st, ctx->opts.nest_timeout);
-    if (!(skip & 16u)) launch_count(d_chunks, d_pages, list(L_COUNT), len(L_COUNT), p.n_count_flat, pairs(L_CDICT), len(L_CDICT) / 2,
-                                       d_res, d_bajobs, st, COUNT_IDLE_GRID);
+    if (!(skip & 16u)) {
+        launch_count_flat(d_chunks, d_pages, list(L_COUNT), len(L_COUNT), p.n_count_flat, pairs(L_CDICT), len(L_CDICT) / 2,
+                          d_res, d_bajobs, st);
+        launch_count(d_chunks, d_pages, list(L_COUNT), len(L_COUNT), d_res, d_bajobs, st, COUNT_IDLE_GRID);
+    }
     launch_nest_count(d_chunks, d_pages, list(L_NEST), n_nest, pairs(L_NSEG), n_nseg, d_res, st);
     if (!(skip & 4u))
         launch_ba(d_bajobs + p.n_ba_dict, n_ba - p.n_ba_dict, d_batiles + p.n_ba_dict_tiles, n_bt - p.n_ba_dict_tiles,

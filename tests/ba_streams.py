@@ -1,7 +1,7 @@
 """PLAIN BYTE_ARRAY value streams that stress the guess-and-verify value walk (TEST INFRASTRUCTURE ONLY).
 
 The walk (k_ba_tile or k_ba_cand / k_ba_link / k_ba_count, k_ba_scan, k_ba_emit, k_ba_verify,
-k_ba_fallback with ba_relink_wg and binary_walk_wg, pf_pages.hip) guesses the <len><bytes> chain from
+k_ba_fallback with ba_relink_wg and binary_walk_wg, pf_ba.hip) guesses the <len><bytes> chain from
 the positions whose 4-byte length fits the stream and verifies the guess. Text never produces a
 fitting length away from a true prefix, so a suite of text never challenges the verification. The
 cases here are binary payloads full of fitting lengths, and text streams whose one interesting prefix
@@ -15,14 +15,14 @@ import numpy as np
 import pagekit as K
 
 # The walk's own constants, restated (never imported).
-BA_TILE = 8192       # pf_internal.h:59   stream bytes per k_ba_* tile
-BA_SHORT = 48        # pf_internal.h:63   page bytes per value up to which a batch takes the fused k_ba_tile
-BA_HALO = 128        # pf_pages.hip:521   k_ba_tile links a successor at most this far from its prefix
-BA_MAX_LINKED = 124  # pf_pages.hip:615   sv - q <= BA_HALO with sv = q + 4 + len: the longest value linked in a tile
-BA_STAGE_END = 176   # pf_pages.hip:524   BA_FSTAGE = 3 * 128 + 8192 + 48 staged from t0 - 256: the stage ends at t1 + 176
-BW_TILE = 1024       # pf_pages.hip:194   binary_walk_wg: stream bytes per tile
-BW_LOOK = 64         # pf_pages.hip:195   binary_walk_wg: staged lookahead
-BW_CAP = 256         # pf_pages.hip:197   binary_walk_wg: candidates per tile
+BA_TILE = 8192       # BA_TILE, pf_internal.h    stream bytes per k_ba_* tile
+BA_SHORT = 48        # BA_SHORT, pf_internal.h   page bytes per value up to which a batch takes the fused k_ba_tile
+BA_HALO = 128        # BA_HALO, pf_ba.hip        k_ba_tile links a successor at most this far from its prefix
+BA_MAX_LINKED = 124  # k_ba_tile, pf_ba.hip      sv - q <= BA_HALO with sv = q + 4 + len: the longest value linked in a tile
+BA_STAGE_END = 176   # BA_FSTAGE, pf_ba.hip      3 * 128 + 8192 + 48 staged from t0 - 256: the stage ends at t1 + 176
+BW_TILE = 1024       # BW_TILE, pf_ba.hip        binary_walk_wg: stream bytes per tile
+BW_LOOK = 64         # BW_LOOK, pf_ba.hip        binary_walk_wg: staged lookahead
+BW_CAP = 256         # BW_CAP, pf_ba.hip         binary_walk_wg: candidates per tile
 MAX_STREAM = 3 * BA_TILE
 
 T1 = BA_TILE         # the first tile's end: where the geometry cases aim
@@ -253,7 +253,7 @@ def straddle_cases():
 def value_end_cases():
     """A value ending exactly at t1, t1 + 127 and t1 + 128 (the end of k_ba_tile's window), and a
     successor prefix at t1 + 172 / 173 / 176 (the last staged length, the first one not staged, the
-    stage end: r + 4 > BA_FSTAGE, pf_pages.hip:599)."""
+    stage end: r + 4 > BA_FSTAGE in k_ba_tile, pf_ba.hip)."""
     out = []
     for end in (0, 127, 128):
         s = _Stream(f"end{end}")
@@ -505,7 +505,7 @@ def stream_residue(info_c):
 
 
 # ---------------------------------------------------------------- the walk's acceptance rules, restated
-# What the filters of pf_pages.hip decide for one walk job (stream, value count), from their stated
+# What the filters of pf_ba.hip decide for one walk job (stream, value count), from their stated
 # rules and in plain numpy: which of the three outcomes a job takes on each route. The GPU tests hold the
 # route counters of every file to these. (The values never depend on the outcome: only the route does.)
 def _links_verify(cand, succ, n, count):

@@ -196,7 +196,7 @@ def test_stream_start_residues(ba_file):
 
 
 def test_restated_rules_give_the_derived_routes():
-    """ba_streams.fused_outcome / multi_kernel_outcome restate the filters of pf_pages.hip; the GPU tests
+    """ba_streams.fused_outcome / multi_kernel_outcome restate the filters of pf_ba.hip; the GPU tests
     hold the route counters to them. Here they must give what the rules say for the cases where that can
     be worked out by hand:
       * text whose values are at most 124 bytes (sv - q <= BA_HALO), wherever the 124-byte value lies:

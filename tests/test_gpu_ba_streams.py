@@ -107,7 +107,7 @@ def _outcome(counts):
 
 def test_route_pins(oracle, ba_dir, switches):
     """One case per decode, so the counters speak of that case's one walk job. The expected counters
-    follow from the rules of the walk (pf_pages.hip), not from a run:
+    follow from the rules of the walk (pf_ba.hip), not from a run:
 
     fused (k_ba_tile, then k_ba_fallback):
       * text of values up to 124 bytes, the 124-byte value at every listed position: every successor is

@@ -1,5 +1,5 @@
 """Nested pages decoded in segments (k_nest_lvl / k_count_seg / k_nest_scan / k_nest_ids /
-k_nest_chars / k_decode_seg, pf_pages.hip): each segment of a page starts from checkpoints of the
+k_nest_chars / k_decode_seg, pf_decode.hip): each segment of a page starts from checkpoints of the
 rep, def and dictionary-id streams instead of walking the page from its first entry. PF_NEST_SEG
 forces the segment path on every eligible nested page with short segments (runs cut mid-way, segments
 without values, segment bounds off the 512-entry tiles), and the results must equal the oracle's,

@@ -6,7 +6,7 @@ the chunk is written with the product's host file writer (pf_writer_*, codec = S
 test_short_runs.py does, and one decode carries jobs of every class at once. Values and validity are
 compared with the numpy source (the assembler's expected bytes) and with the oracle; per job
 pf_debug_snappy_fallback and per page pf_debug_page_direct must be the code read off k_snappy_head
-(pf_pages.hip) -- the table in _pages() names the line that decides each.
+(pf_snappy_head.hip) -- the table in _pages() names the line that decides each.
 
 Columns: REQUIRED INT64 PLAIN, 5000 values a page (no level section: dlo = 0); OPTIONAL INT64 PLAIN with
 every value present (the page statistics say null_count = 0, as parquet-mr's and Arrow's do, except on
@@ -105,7 +105,7 @@ def _compressible(straddle=False, split_head=False):
 
 def _pages(optional):
     """[(name, body builder, pf_debug_snappy_fallback, pf_debug_page_direct)] with the line of
-    k_snappy_head (pf_pages.hip) that decides."""
+    k_snappy_head (pf_snappy_head.hip) that decides."""
     pages = [
         # "if (one) { pg.body = in + data; pg.direct = DIRECT_INPLACE; fb[j] = FB_INPLACE; }"
         ("one_literal", _one_literal(), FB_INPLACE, DIRECT_INPLACE),
