@@ -297,6 +297,13 @@ const char* pf_file_created_by(pf_file* f);
  *      DictionaryValuesWriter), RLE/bit-packed hybrid ids, PLAIN values, Snappy compression of
  *      every page. Flat schemas of the types the reference writes (ParquetWriter.java:143-157):
  *      BOOLEAN, INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY (UTF8). ---- */
+/* pf_encode_column.dictionary is a bit set (0 and 1 keep the meaning they always had). */
+#define PF_ENCODE_DICTIONARY     1   /* dictionary-encode; the chunk falls back as a whole above
+                                        dict_page_limit, on a hash collision, or for BOOLEAN */
+#define PF_ENCODE_DELTA_FALLBACK 2   /* a chunk that is not dictionary-encoded (bit 0 clear, or any fallback)
+                                        gets the encodings parquet-mr's PARQUET_2_0 writer falls back to:
+                                        DELTA_BINARY_PACKED (INT32, INT64), DELTA_BYTE_ARRAY (BYTE_ARRAY);
+                                        FLOAT, DOUBLE and BOOLEAN stay PLAIN. Clear: PLAIN */
 typedef struct pf_encode_column {
     int32_t  physical_type;       /* PF_BOOLEAN, PF_INT32, PF_INT64, PF_FLOAT, PF_DOUBLE, PF_BYTE_ARRAY */
     int32_t  max_def;             /* 0 = REQUIRED, 1 = OPTIONAL */
@@ -306,7 +313,8 @@ typedef struct pf_encode_column {
     const int32_t* offsets;       /* BYTE_ARRAY: num_rows + 1 (null rows: empty) */
     const uint8_t* chars;         /* BYTE_ARRAY */
     int64_t  chars_len;
-    int32_t  dictionary;          /* 1: dictionary-encode (PLAIN above dict_page_limit or on a hash collision) */
+    int32_t  dictionary;          /* PF_ENCODE_* bits; 1: dictionary-encode (PLAIN above dict_page_limit or on a
+                                     hash collision), 3: the same with the DELTA_* fallback, 2: DELTA_* pages */
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
     int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's) or PF_CODEC_UNCOMPRESSED */
@@ -322,11 +330,12 @@ typedef struct pf_encoded_chunk {
     int64_t  data_page_offset;         /* relative to bytes */
     int32_t  n_data_pages;
     int32_t  dict_entries;        /* 0 when not dictionary-encoded */
-    int32_t  data_encoding;       /* PF_ENC_RLE_DICTIONARY or PF_ENC_PLAIN */
+    int32_t  data_encoding;       /* PF_ENC_RLE_DICTIONARY or PF_ENC_PLAIN; with PF_ENCODE_DELTA_FALLBACK also
+                                     PF_ENC_DELTA_BINARY_PACKED / PF_ENC_DELTA_BYTE_ARRAY */
     int32_t  fallback;            /* 0; 1 dictionary above the limit; 2 hash collision; 3 type (BOOLEAN) */
     int32_t  codec;               /* ColumnMetaData.codec */
     float    snappy_ms;           /* k_snappy_compress time (HIP events; 0 when stage timing is off) */
-    float    encode_ms;           /* dictionary + page kernels time (HIP events; 0 when timing is off) */
+    float    encode_ms;           /* dictionary + page (PLAIN, ids, DELTA_*) kernels time (HIP events; 0 when timing is off) */
     int64_t  snappy_in, snappy_out;    /* bytes into / out of the compressor */
 } pf_encoded_chunk;
 

@@ -60,6 +60,40 @@ struct EncArgs {
     uint8_t* vals_out;               // data pages' values sections
 };
 
+// ---- DELTA_BINARY_PACKED / DELTA_BYTE_ARRAY pages (pf_enc_delta.hip) ----
+// One DELTA_BINARY_PACKED stream: `cnt` elements of `ew` bytes (4 | 8, signed) at `src`. Its items in
+// the size table are item0 (the stream header) and one per 128-delta block after it.
+struct DeltaStream {
+    const uint8_t* src;
+    uint32_t ew, cnt, page, item0;
+};
+
+// A data page: streams [s0, s0 + ns) back to back (integers: 1; strings: prefix lengths, suffix
+// lengths, followed by the suffix bytes) over dense values [d0, d0 + cnt).
+struct DeltaPage {
+    uint64_t out_off;   // values section in `out` (known after the size pass)
+    uint32_t d0, cnt, s0, ns;
+};
+
+struct DeltaArgs {
+    const DeltaStream* streams;      // n_streams + 1 (the last: item0 = n_items)
+    const DeltaPage* pages;          // n_pages
+    uint32_t n_streams, n_pages, n_items;
+    uint32_t* bytes;                 // n_items + 1: bytes of every item
+    uint32_t* off;                   // n_items + 1 (exclusive scan of bytes)
+    long long* minv;                 // n_items: min delta of a block
+    uint32_t* widths;                // n_items: the 4 miniblock widths, one byte each
+    uint32_t* totals;                // n_pages: bytes of a page's values section
+    uint32_t* pfx;                   // strings, m + 1: prefix length
+    uint32_t* sfx;                   // strings, m + 1: suffix length
+    uint32_t* spre;                  // strings, m + 1 (exclusive scan of sfx); nullptr for integers
+    uint8_t* out;                    // data pages' values sections
+};
+
+hipError_t enc_delta_prefix(const EncArgs& a, const DeltaArgs& t, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t enc_delta_sizes(const DeltaArgs& t, void* temp, size_t temp_bytes, hipStream_t st);
+void enc_delta_write(const EncArgs& a, const DeltaArgs& t, uint32_t m, hipStream_t st);
+
 hipError_t enc_scan_temp(size_t n, size_t& bytes);
 hipError_t enc_dense(const EncArgs& a, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t enc_plain_sizes(const EncArgs& a, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);

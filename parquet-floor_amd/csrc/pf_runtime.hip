@@ -533,6 +533,27 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         pp.push_back(p);
         if (n == 0) break;
     }
+    // DELTA_* fallback (PF_ENCODE_DELTA_FALLBACK): one stream per integer page, two (prefix lengths,
+    // suffix lengths) per string page; an item of the size table is a stream header or a 128-delta block
+    const bool delta_bit = (col->dictionary & PF_ENCODE_DELTA_FALLBACK) && (pt == PF_INT32 || pt == PF_INT64 || str);
+    std::vector<DeltaStream> dstreams;
+    std::vector<DeltaPage> dpages;
+    uint32_t n_items = 0;
+    if (delta_bit) {
+        for (size_t i = 0; i < pp.size(); i++) {
+            const PagePlanE& p = pp[i];
+            const uint32_t ns = str ? 2u : 1u, blocks = p.cnt > 1 ? (p.cnt - 1 + 127) / 128 : 0u;
+            // worst case of the values section (every block: zigzag(min) + widths + full-width values)
+            const uint64_t worst = ns * (25ull + blocks * 14ull + uint64_t(p.cnt) * (str ? 4 : w)) + (str ? p.plain : 0);
+            if (worst > 0x7fffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
+            dpages.push_back(DeltaPage{0, p.d0, p.cnt, uint32_t(dstreams.size()), ns});
+            for (uint32_t k = 0; k < ns; k++) {
+                dstreams.push_back(DeltaStream{nullptr, uint32_t(str ? 4 : w), p.cnt, uint32_t(i), n_items});
+                n_items += 1 + blocks;
+            }
+        }
+        dstreams.push_back(DeltaStream{nullptr, 0, 0, 0, n_items});
+    }
 
     // ---- device arena ----
     size_t a_sz = 0;
@@ -546,8 +567,16 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     const size_t o_key = take(a_sz, 8 * N1), o_skey = take(a_sz, 8 * N1), o_didx = take(a_sz, 4 * N1), o_sidx = take(a_sz, 4 * N1);
     const size_t o_hp = take(a_sz, 4 * N1), o_head = take(a_sz, 4 * N1), o_mark = take(a_sz, 4 * N1), o_did = take(a_sz, 4 * N1);
     const size_t o_dsz = take(a_sz, 4 * N1), o_doff = take(a_sz, 4 * N1), o_ids = take(a_sz, 4 * N1), o_col = take(a_sz, 256);
+    // DELTA_* tables (only with the bit set): string prefix / suffix lengths and positions, streams, pages,
+    // item bytes and offsets, block minima and widths, page totals
+    const size_t NI1 = delta_bit ? size_t(n_items) + 1 : 0;
+    const size_t o_pfx = take(a_sz, delta_bit && str ? 4 * N1 : 0), o_sfx = take(a_sz, delta_bit && str ? 4 * N1 : 0);
+    const size_t o_spre = take(a_sz, delta_bit && str ? 4 * N1 : 0);
+    const size_t o_dstr = take(a_sz, sizeof(DeltaStream) * dstreams.size()), o_dpg = take(a_sz, sizeof(DeltaPage) * dpages.size());
+    const size_t o_dby = take(a_sz, 4 * NI1), o_dof = take(a_sz, 4 * NI1), o_dmin = take(a_sz, 8 * NI1), o_dwd = take(a_sz, 4 * NI1);
+    const size_t o_dtot = take(a_sz, 4 * dpages.size());
     size_t temp_bytes = 0;
-    HIPCHK(ctx, enc_scan_temp(N1, temp_bytes));
+    HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
     const size_t o_temp = take(a_sz, temp_bytes);
     HIPCHK(ctx, ctx->d_enc.ensure(a_sz));
     uint8_t* A = static_cast<uint8_t*>(ctx->d_enc.p);
@@ -591,7 +620,8 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     // (all values distinct: 4 m + chars) is written PLAIN (conservative: such a dictionary is over any
     // page limit unless most values repeat; parity with parquet-mr's writer is unpinned).
     const bool dict_fits32 = !str || 4ull * uint64_t(m) + uint64_t(col->chars_len) < (1ull << 32);
-    const bool want_dict = col->dictionary && pt != PF_BOOLEAN && m > 0 && dict_fits32;
+    const bool dict_bit = (col->dictionary & PF_ENCODE_DICTIONARY) != 0;
+    const bool want_dict = dict_bit && pt != PF_BOOLEAN && m > 0 && dict_fits32;
     uint32_t hres[3] = {0, 0, 0};   // collide, dictionary entries, dictionary bytes
     float enc_ms = 0.f;
     if (want_dict) {
@@ -604,9 +634,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         if (ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&enc_ms, ctx->ev[2], ctx->ev[3]));
     }
     int fallback = 0;
-    if (col->dictionary && pt == PF_BOOLEAN) fallback = 3;
+    if (dict_bit && pt == PF_BOOLEAN) fallback = 3;
     else if (want_dict && hres[0]) fallback = 2;
-    else if (col->dictionary && pt != PF_BOOLEAN && m > 0 && !dict_fits32) fallback = 1;
+    else if (dict_bit && pt != PF_BOOLEAN && m > 0 && !dict_fits32) fallback = 1;
     else if (want_dict && (str ? int64_t(hres[2]) : int64_t(hres[1]) * w) > dict_limit) fallback = 1;   // fixed: D * w on the host
     const bool dict = want_dict && fallback == 0;
     const uint32_t D = dict ? hres[1] : 0, dict_bytes = dict ? (str ? hres[2] : hres[1] * uint32_t(w)) : 0;
@@ -614,35 +644,79 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     while (D > 1 && (uint64_t(1) << bw) < D) bw++;
 
     // ---- values sections: [dictionary page | page 0 | page 1 | ...] in d_enc_out's front ----
-    std::vector<EncPage> ep(pp.size());
+    const bool delta = delta_bit && !dict;   // the chunk is not dictionary-encoded: DELTA_* pages
+    const int data_enc = dict ? PF_ENC_RLE_DICTIONARY : delta ? (str ? PF_ENC_DELTA_BYTE_ARRAY : PF_ENC_DELTA_BINARY_PACKED) : PF_ENC_PLAIN;
+    std::vector<EncPage> ep(delta ? 0 : pp.size());
     std::vector<std::pair<uint64_t, uint64_t>> sections;
     size_t vo = 0;
     const size_t o_dict = take(vo, dict_bytes);
     if (dict) sections.push_back({o_dict, dict_bytes});
-    for (size_t i = 0; i < pp.size(); i++) {
-        const PagePlanE& p = pp[i];
-        uint64_t bytes;
-        if (dict) {
-            const uint64_t groups = (p.cnt + 7) / 8;
-            bytes = p.cnt ? 1 + uvarint_len((groups << 1) | 1) + groups * bw : 1;
-        } else {
-            bytes = p.plain;
+    if (delta) {
+        // size pass -> scan -> page totals (one D2H, one sync) -> sections -> write pass
+        DeltaArgs da{};
+        da.streams = reinterpret_cast<const DeltaStream*>(A + o_dstr);
+        da.pages = reinterpret_cast<const DeltaPage*>(A + o_dpg);
+        da.n_streams = uint32_t(dstreams.size() - 1); da.n_pages = uint32_t(dpages.size()); da.n_items = n_items;
+        da.bytes = reinterpret_cast<uint32_t*>(A + o_dby); da.off = reinterpret_cast<uint32_t*>(A + o_dof);
+        da.minv = reinterpret_cast<long long*>(A + o_dmin); da.widths = reinterpret_cast<uint32_t*>(A + o_dwd);
+        da.totals = reinterpret_cast<uint32_t*>(A + o_dtot);
+        if (str) {
+            da.pfx = reinterpret_cast<uint32_t*>(A + o_pfx); da.sfx = reinterpret_cast<uint32_t*>(A + o_sfx);
+            da.spre = reinterpret_cast<uint32_t*>(A + o_spre);
         }
-        ep[i] = EncPage{0, p.d0, p.cnt, dict ? 1u : 0u, bw};
-        ep[i].out_off = take(vo, bytes);
-        sections.push_back({ep[i].out_off, bytes});
+        for (size_t s = 0; s + 1 < dstreams.size(); s++) {
+            const DeltaPage& p = dpages[dstreams[s].page];
+            dstreams[s].src = !str ? ea.dense + uint64_t(p.d0) * uint32_t(w)
+                                   : reinterpret_cast<const uint8_t*>((s - p.s0 == 0 ? da.pfx : da.sfx) + p.d0);
+        }
+        EVREC(ctx, ctx->ev[4], st);
+        HIPCHK(ctx, hipMemcpyAsync(A + o_dstr, dstreams.data(), sizeof(DeltaStream) * dstreams.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(A + o_dpg, dpages.data(), sizeof(DeltaPage) * dpages.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(da.bytes + n_items, 0, 4, st));
+        if (str) HIPCHK(ctx, enc_delta_prefix(ea, da, m, temp, temp_bytes, st));
+        HIPCHK(ctx, enc_delta_sizes(da, temp, temp_bytes, st));
+        std::vector<uint32_t> htot(dpages.size());
+        HIPCHK(ctx, hipMemcpyAsync(htot.data(), da.totals, 4 * htot.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        for (size_t i = 0; i < dpages.size(); i++) {
+            if (htot[i] > 0x7fffffffu) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
+            dpages[i].out_off = take(vo, htot[i]);
+            sections.push_back({dpages[i].out_off, htot[i]});
+        }
+        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
+        da.out = static_cast<uint8_t*>(ctx->d_enc_sec.p);
+        HIPCHK(ctx, hipMemcpyAsync(A + o_dpg, dpages.data(), sizeof(DeltaPage) * dpages.size(), hipMemcpyHostToDevice, st));
+        enc_delta_write(ea, da, m, st);
+        HIPCHK(ctx, hipGetLastError());
+        EVREC(ctx, ctx->ev[5], st);
     }
-    const size_t o_pages = take(vo, sizeof(EncPage) * ep.size());
-    HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
     uint8_t* SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
-    ea.dict_out = SEC + o_dict;
-    ea.vals_out = SEC;
-    EVREC(ctx, ctx->ev[4], st);
-    if (dict) enc_dictionary_page_and_ids(ea, m, st);
-    HIPCHK(ctx, hipMemcpyAsync(SEC + o_pages, ep.data(), sizeof(EncPage) * ep.size(), hipMemcpyHostToDevice, st));
-    enc_pages(ea, reinterpret_cast<const EncPage*>(SEC + o_pages), int(ep.size()), st);
-    HIPCHK(ctx, hipGetLastError());
-    EVREC(ctx, ctx->ev[5], st);
+    if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size
+        for (size_t i = 0; i < pp.size(); i++) {
+            const PagePlanE& p = pp[i];
+            uint64_t bytes;
+            if (dict) {
+                const uint64_t groups = (p.cnt + 7) / 8;
+                bytes = p.cnt ? 1 + uvarint_len((groups << 1) | 1) + groups * bw : 1;
+            } else {
+                bytes = p.plain;
+            }
+            ep[i] = EncPage{0, p.d0, p.cnt, dict ? 1u : 0u, bw};
+            ep[i].out_off = take(vo, bytes);
+            sections.push_back({ep[i].out_off, bytes});
+        }
+        const size_t o_pages = take(vo, sizeof(EncPage) * ep.size());
+        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
+        SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
+        ea.dict_out = SEC + o_dict;
+        ea.vals_out = SEC;
+        EVREC(ctx, ctx->ev[4], st);
+        if (dict) enc_dictionary_page_and_ids(ea, m, st);
+        HIPCHK(ctx, hipMemcpyAsync(SEC + o_pages, ep.data(), sizeof(EncPage) * ep.size(), hipMemcpyHostToDevice, st));
+        enc_pages(ea, reinterpret_cast<const EncPage*>(SEC + o_pages), int(ep.size()), st);
+        HIPCHK(ctx, hipGetLastError());
+        EVREC(ctx, ctx->ev[5], st);
+    }
     std::vector<std::vector<uint8_t>> bodies;
     float snap_ms = 0.f;
     if (col->codec == PF_CODEC_SNAPPY) {
@@ -698,7 +772,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         h.num_values = int32_t(rows);
         h.num_nulls = int32_t(rows - p.cnt);
         h.num_rows = int32_t(rows);
-        h.encoding = dict ? PF_ENC_RLE_DICTIONARY : PF_ENC_PLAIN;
+        h.encoding = data_enc;
         h.def_bytes = int32_t(def.size());
         h.is_compressed = col->codec == PF_CODEC_SNAPPY;
         const size_t h0 = o.size();
@@ -713,7 +787,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     out->num_values = n;
     out->n_data_pages = int32_t(pp.size());
     out->dict_entries = int32_t(D);
-    out->data_encoding = dict ? PF_ENC_RLE_DICTIONARY : PF_ENC_PLAIN;
+    out->data_encoding = data_enc;
     out->fallback = fallback;
     out->codec = col->codec;
     if (ctx->timing) {   // the page kernels' events have completed (the stream was synchronised since)

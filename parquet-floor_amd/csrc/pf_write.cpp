@@ -218,9 +218,12 @@ int pf_writer_close(pf_writer* w) {
                 t.i64(2, c.file_offset);
                 t.begin_struct(3);   // ColumnMetaData
                 t.i32(1, w->fields[i].physical_type);
+                // the encodings the chunk uses: RLE levels; PLAIN values, or a PLAIN dictionary page with
+                // RLE_DICTIONARY ids; a DELTA_* chunk has no PLAIN page
                 const bool dict = c.data_encoding == PF_ENC_RLE_DICTIONARY;
+                const bool delta = c.data_encoding == PF_ENC_DELTA_BINARY_PACKED || c.data_encoding == PF_ENC_DELTA_BYTE_ARRAY;
                 t.list_header(2, T_I32, dict ? 3 : 2);
-                t.zigzag(PF_ENC_PLAIN);
+                t.zigzag(delta ? c.data_encoding : PF_ENC_PLAIN);
                 t.zigzag(PF_ENC_RLE);
                 if (dict) t.zigzag(PF_ENC_RLE_DICTIONARY);
                 t.list_header(3, T_BINARY, 1);

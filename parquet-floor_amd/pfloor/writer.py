@@ -4,14 +4,20 @@ Dehydrator.java, ValueWriter.java) over the GPU write path of libpfloor.so (SURV
 ParquetWriter.writeFile(schema, file, dehydrator) -> writer; writer.write(record); writer.close().
 Like the reference (ParquetWriter.java:61-68) every column is SNAPPY-compressed with the
 PARQUET_2_0 writer settings of parquet-mr 1.12.2: data pages v2 of 20,000 rows, dictionary
-encoding with PLAIN fallback above the 1 MiB dictionary page size. Records are buffered per
+encoding with a whole-chunk fallback above the 1 MiB dictionary page size. Records are buffered per
 row group on the host (dehydrated column by column, SimpleWriteSupport.writeField :143-160) and
-each column chunk is encoded on the GPU (pf_encode_chunk: dictionary build, ids, PLAIN values,
-Snappy), then appended with its page headers by the host file writer (pf_writer_*).
+each column chunk is encoded on the GPU (pf_encode_chunk: dictionary build, ids, PLAIN or DELTA_*
+values, Snappy), then appended with its page headers by the host file writer (pf_writer_*).
 
-Differences that are allowed by the format and documented in DESIGN.md: the fallback encoding is
-PLAIN (parquet-mr's v2 writer falls back to DELTA_* for ints / strings), ids are written as one
-bit-packed run per page, no page / column statistics are written.
+The fallback encoding is PLAIN by default. With delta_fallback=True a chunk that is not
+dictionary-encoded is written as parquet-mr's v2 writer writes it: DELTA_BINARY_PACKED (INT32,
+INT64) or DELTA_BYTE_ARRAY (BINARY) data pages, encoded on the GPU in parquet-mr's stream layout;
+FLOAT, DOUBLE and BOOLEAN stay PLAIN.
+
+Differences that are allowed by the format and documented in DESIGN.md: the fallback is decided
+for the whole chunk (parquet-mr switches mid-chunk and also drops a dictionary that does not
+compress, isCompressionSatisfying), ids are written as one bit-packed run per page, no page /
+column statistics are written.
 """
 import ctypes as C
 
@@ -21,6 +27,7 @@ from . import _native
 from ._native import PfError, check, lib
 
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1, 2, 3, 4, 5, 6, 7
+ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK = 1, 2   # pf_encode_column.dictionary bits (PF_ENCODE_*)
 _WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, FLOAT: 4, DOUBLE: 8}
 _DTYPE = {BOOLEAN: np.uint8, INT32: np.int32, INT64: np.int64, FLOAT: np.float32, DOUBLE: np.float64}
 _NAMES = {BOOLEAN: "BOOLEAN", INT32: "INT32", INT64: "INT64", INT96: "INT96", FLOAT: "FLOAT", DOUBLE: "DOUBLE",
@@ -171,7 +178,10 @@ class GpuColumnEncoder:
     def __init__(self, decoder):
         self.dec = decoder
 
-    def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1):
+    def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1,
+               delta_fallback=False):
+        """delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
+        dictionary-encoded (INT32, INT64, BINARY)."""
         c = EncodeColumn()
         c.physical_type = field.physical_type
         c.max_def = 1 if field.optional else 0
@@ -195,7 +205,7 @@ class GpuColumnEncoder:
             v = np.ascontiguousarray(validity, np.uint8)
             keep.append(v)
             c.validity = v.ctypes.data
-        c.dictionary = 1 if dictionary else 0
+        c.dictionary = (ENCODE_DICTIONARY if dictionary else 0) | (ENCODE_DELTA_FALLBACK if delta_fallback else 0)
         c.page_rows = page_rows
         c.dict_page_limit = dict_page_limit
         c.codec = codec
@@ -210,8 +220,9 @@ class ParquetWriter:
     block size; the bound here is in rows, the byte size of a row group is the caller's)."""
 
     def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=1,
-                 decoders=None):
-        """decoders: several contexts (GpuDecoder) to encode the columns of a row group in parallel
+                 decoders=None, delta_fallback=False):
+        """delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
+        decoders: several contexts (GpuDecoder) to encode the columns of a row group in parallel
         (one host thread each); chunks are still appended in schema order."""
         from .decoder import GpuDecoder
         self.schema, self.dehydrator = schema, dehydrator
@@ -222,6 +233,7 @@ class ParquetWriter:
         self.encoders = [GpuColumnEncoder(d) for d in decoders] if decoders else [self.enc]
         self.kernel_ms = {"snappy": 0.0, "encode": 0.0, "snappy_in": 0, "snappy_out": 0}
         self.codec = codec
+        self.delta_fallback = delta_fallback
         self.buf = _RowBuffer(schema)
         self.last_chunks = []     # (dict_entries, data_encoding, fallback) of the last row group
         fields = (WriteField * len(schema.fields))()
@@ -286,7 +298,7 @@ class ParquetWriter:
                             return
                         i = order.pop(0)
                     f, d, validity = work[i]
-                    out = enc.encode(f, d, validity, n, codec=self.codec)
+                    out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback)
                     keep = C.create_string_buffer(C.string_at(out.bytes, out.size), max(1, out.size))
                     cp = EncodedChunk.from_buffer_copy(out)
                     cp.bytes = C.cast(keep, C.c_void_p)
@@ -313,7 +325,7 @@ class ParquetWriter:
             raise PfError(rc, "pf_writer_add_chunk: " + (lib().pf_writer_last_error() or b"").decode(errors="replace"))
 
     def _encode_add(self, f, data, validity, n, i):
-        out = self.enc.encode(f, data, validity, n, codec=self.codec)
+        out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback)
         self._add(out, i)
         return out
 
