@@ -304,6 +304,13 @@ const char* pf_file_created_by(pf_file* f);
                                         gets the encodings parquet-mr's PARQUET_2_0 writer falls back to:
                                         DELTA_BINARY_PACKED (INT32, INT64), DELTA_BYTE_ARRAY (BYTE_ARRAY);
                                         FLOAT, DOUBLE and BOOLEAN stay PLAIN. Clear: PLAIN */
+#define PF_ENCODE_HYBRID_RUNS    4   /* RLE / bit-packed hybrid streams in the run shape of parquet-mr's
+                                        RunLengthBitPackingHybridEncoder (RLE runs of >= 8 repeats between
+                                        bit-packed groups), encoded on the GPU: the ids of RLE_DICTIONARY pages
+                                        (width of dict_entries - 1: 0 for one entry), the definition levels of
+                                        an OPTIONAL column whatever its values' encoding, and BOOLEAN values
+                                        (PF_ENC_RLE: 4-byte length + stream). Clear: ids and levels are one
+                                        bit-packed run per page, BOOLEAN is PLAIN */
 typedef struct pf_encode_column {
     int32_t  physical_type;       /* PF_BOOLEAN, PF_INT32, PF_INT64, PF_FLOAT, PF_DOUBLE, PF_BYTE_ARRAY */
     int32_t  max_def;             /* 0 = REQUIRED, 1 = OPTIONAL */
@@ -314,7 +321,8 @@ typedef struct pf_encode_column {
     const uint8_t* chars;         /* BYTE_ARRAY */
     int64_t  chars_len;
     int32_t  dictionary;          /* PF_ENCODE_* bits; 1: dictionary-encode (PLAIN above dict_page_limit or on a
-                                     hash collision), 3: the same with the DELTA_* fallback, 2: DELTA_* pages */
+                                     hash collision), 3: the same with the DELTA_* fallback, 2: DELTA_* pages;
+                                     | 4: parquet-mr's hybrid runs (7 = the encodings of its PARQUET_2_0 writer) */
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
     int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's) or PF_CODEC_UNCOMPRESSED */
@@ -331,11 +339,12 @@ typedef struct pf_encoded_chunk {
     int32_t  n_data_pages;
     int32_t  dict_entries;        /* 0 when not dictionary-encoded */
     int32_t  data_encoding;       /* PF_ENC_RLE_DICTIONARY or PF_ENC_PLAIN; with PF_ENCODE_DELTA_FALLBACK also
-                                     PF_ENC_DELTA_BINARY_PACKED / PF_ENC_DELTA_BYTE_ARRAY */
+                                     PF_ENC_DELTA_BINARY_PACKED / PF_ENC_DELTA_BYTE_ARRAY; with
+                                     PF_ENCODE_HYBRID_RUNS PF_ENC_RLE for BOOLEAN */
     int32_t  fallback;            /* 0; 1 dictionary above the limit; 2 hash collision; 3 type (BOOLEAN) */
     int32_t  codec;               /* ColumnMetaData.codec */
     float    snappy_ms;           /* k_snappy_compress time (HIP events; 0 when stage timing is off) */
-    float    encode_ms;           /* dictionary + page (PLAIN, ids, DELTA_*) kernels time (HIP events; 0 when timing is off) */
+    float    encode_ms;           /* dictionary + page (PLAIN, ids, DELTA_*, hybrid runs) kernels time (HIP events; 0 when timing is off) */
     int64_t  snappy_in, snappy_out;    /* bytes into / out of the compressor */
 } pf_encoded_chunk;
 

@@ -94,6 +94,28 @@ hipError_t enc_delta_prefix(const EncArgs& a, const DeltaArgs& t, uint32_t m, vo
 hipError_t enc_delta_sizes(const DeltaArgs& t, void* temp, size_t temp_bytes, hipStream_t st);
 void enc_delta_write(const EncArgs& a, const DeltaArgs& t, uint32_t m, hipStream_t st);
 
+// ---- RLE / bit-packed hybrid streams in parquet-mr's run shape (pf_enc_hybrid.hip) ----
+enum { HY_VALIDITY = 0, HY_IDS = 1, HY_BOOL = 2 };                 // HybridStream.kind
+enum { HY_PREFIX_NONE = 0, HY_PREFIX_WIDTH = 1, HY_PREFIX_LENGTH = 2 };   // bytes in front of out_off
+
+// One stream: `cnt` entries from entry `first` of `src` at bit width `bw`: the validity bits of a page's
+// rows (nullptr: all set), the uint32 dictionary ids or the dense BOOLEAN bytes of its present values.
+struct HybridStream {
+    const uint8_t* src;
+    uint64_t out_off;   // first byte of the stream in `out` (known after the size pass)
+    uint32_t kind, first, cnt, bw, prefix, page;
+};
+
+struct HybridArgs {
+    const HybridStream* streams;     // n_streams
+    uint32_t n_streams;
+    uint32_t* bytes;                 // n_streams: bytes of every stream (size pass)
+    uint8_t* out;
+};
+
+hipError_t enc_hybrid_sizes(const HybridArgs& t, hipStream_t st);
+void enc_hybrid_write(const HybridArgs& t, hipStream_t st);
+
 hipError_t enc_scan_temp(size_t n, size_t& bytes);
 hipError_t enc_dense(const EncArgs& a, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t enc_plain_sizes(const EncArgs& a, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);

@@ -10,7 +10,8 @@
 //   data pages   -> values section per page: bit width byte + one bit-packed run of the ids
 //                   (RLE_DICTIONARY), or PLAIN; definition levels (v2 pages, bit width 1) are the
 //                   validity bits themselves, written by the host; DELTA_BINARY_PACKED /
-//                   DELTA_BYTE_ARRAY values sections: pf_enc_delta.hip
+//                   DELTA_BYTE_ARRAY values sections: pf_enc_delta.hip; ids, levels and BOOLEAN values
+//                   in parquet-mr's run shape (PF_ENCODE_HYBRID_RUNS): pf_enc_hybrid.hip
 //   Snappy       -> k_snappy_compress: one wave per 8 KiB job (hash table of 4-byte
 //                   prefixes in LDS, 64 candidate positions per step, wave-parallel match
 //                   extension); jobs are independent, so a page's stream is the varint length

@@ -554,6 +554,10 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         }
         dstreams.push_back(DeltaStream{nullptr, 0, 0, 0, n_items});
     }
+    // parquet-mr's hybrid runs (PF_ENCODE_HYBRID_RUNS): a page has a stream of levels (OPTIONAL) and one of
+    // ids or BOOLEAN values
+    const bool hyb = (col->dictionary & PF_ENCODE_HYBRID_RUNS) != 0;
+    const size_t n_hs_max = hyb ? 2 * pp.size() : 0;
 
     // ---- device arena ----
     size_t a_sz = 0;
@@ -575,6 +579,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     const size_t o_dstr = take(a_sz, sizeof(DeltaStream) * dstreams.size()), o_dpg = take(a_sz, sizeof(DeltaPage) * dpages.size());
     const size_t o_dby = take(a_sz, 4 * NI1), o_dof = take(a_sz, 4 * NI1), o_dmin = take(a_sz, 8 * NI1), o_dwd = take(a_sz, 4 * NI1);
     const size_t o_dtot = take(a_sz, 4 * dpages.size());
+    const size_t o_hstr = take(a_sz, sizeof(HybridStream) * n_hs_max), o_hby = take(a_sz, 4 * n_hs_max);
     size_t temp_bytes = 0;
     HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
     const size_t o_temp = take(a_sz, temp_bytes);
@@ -642,15 +647,76 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     const uint32_t D = dict ? hres[1] : 0, dict_bytes = dict ? (str ? hres[2] : hres[1] * uint32_t(w)) : 0;
     uint32_t bw = 1;
     while (D > 1 && (uint64_t(1) << bw) < D) bw++;
+    if (hyb && D == 1) bw = 0;   // parquet-mr's getWidthFromMaxInt(D - 1)
+    const bool brle = hyb && pt == PF_BOOLEAN;   // parquet-mr v2 writes BOOLEAN with the RLE encoding
 
     // ---- values sections: [dictionary page | page 0 | page 1 | ...] in d_enc_out's front ----
     const bool delta = delta_bit && !dict;   // the chunk is not dictionary-encoded: DELTA_* pages
-    const int data_enc = dict ? PF_ENC_RLE_DICTIONARY : delta ? (str ? PF_ENC_DELTA_BYTE_ARRAY : PF_ENC_DELTA_BINARY_PACKED) : PF_ENC_PLAIN;
+    const int data_enc = dict ? PF_ENC_RLE_DICTIONARY : delta ? (str ? PF_ENC_DELTA_BYTE_ARRAY : PF_ENC_DELTA_BINARY_PACKED)
+                              : brle ? PF_ENC_RLE : PF_ENC_PLAIN;
     std::vector<EncPage> ep(delta ? 0 : pp.size());
     std::vector<std::pair<uint64_t, uint64_t>> sections;
     size_t vo = 0;
     const size_t o_dict = take(vo, dict_bytes);
     if (dict) sections.push_back({o_dict, dict_bytes});
+    // Hybrid streams: size pass (after the ids, which it reads) -> the streams' bytes in one D2H and one sync ->
+    // the host sizes the sections and the levels -> write pass over the same grid.
+    std::vector<HybridStream> hs;
+    std::vector<uint32_t> hbytes;
+    std::vector<int> lv_of(pp.size(), -1), vs_of(pp.size(), -1);   // a page's level / value stream
+    std::vector<size_t> lv_off(pp.size(), 0);                       // a page's levels in hlv
+    size_t o_lv = 0, lv_total = 0;
+    HybridArgs ha{};
+    auto hybrid_sizes = [&]() -> int {
+        for (size_t i = 0; i < pp.size() && col->max_def == 1; i++) {
+            lv_of[i] = int(hs.size());
+            hs.push_back(HybridStream{ea.validity, 0, HY_VALIDITY, uint32_t(pp[i].r0), uint32_t(pp[i].r1 - pp[i].r0), 1,
+                                      HY_PREFIX_NONE, uint32_t(i)});
+        }
+        for (size_t i = 0; i < pp.size() && (dict || brle); i++) {
+            vs_of[i] = int(hs.size());
+            hs.push_back(dict ? HybridStream{reinterpret_cast<const uint8_t*>(ea.ids), 0, HY_IDS, pp[i].d0, pp[i].cnt, bw,
+                                             HY_PREFIX_WIDTH, uint32_t(i)}
+                              : HybridStream{ea.dense, 0, HY_BOOL, pp[i].d0, pp[i].cnt, 1, HY_PREFIX_LENGTH, uint32_t(i)});
+        }
+        ha.streams = reinterpret_cast<const HybridStream*>(A + o_hstr);
+        ha.n_streams = uint32_t(hs.size());
+        ha.bytes = reinterpret_cast<uint32_t*>(A + o_hby);
+        hbytes.assign(hs.size(), 0);
+        EVREC(ctx, ctx->ev[6], st);
+        if (dict) enc_dictionary_page_and_ids(ea, m, st);
+        if (!hs.empty()) {
+            HIPCHK(ctx, hipMemcpyAsync(A + o_hstr, hs.data(), sizeof(HybridStream) * hs.size(), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, enc_hybrid_sizes(ha, st));
+        }
+        EVREC(ctx, ctx->ev[7], st);
+        if (!hs.empty()) HIPCHK(ctx, hipMemcpyAsync(hbytes.data(), ha.bytes, 4 * hs.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        if (ctx->timing) {
+            float ms = 0.f;
+            HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
+            enc_ms += ms;
+        }
+        return PF_OK;
+    };
+    auto place_levels = [&](size_t& cur) {   // the pages' levels, back to back behind the values sections
+        for (size_t i = 0; i < pp.size(); i++)
+            if (lv_of[i] >= 0) { lv_off[i] = lv_total; lv_total += hbytes[size_t(lv_of[i])]; }
+        o_lv = take(cur, lv_total);
+        for (size_t i = 0; i < pp.size(); i++)
+            if (lv_of[i] >= 0) hs[size_t(lv_of[i])].out_off = o_lv + lv_off[i];
+    };
+    auto hybrid_write = [&](uint8_t* out) -> int {
+        if (hs.empty()) return PF_OK;
+        ha.out = out;
+        HIPCHK(ctx, hipMemcpyAsync(A + o_hstr, hs.data(), sizeof(HybridStream) * hs.size(), hipMemcpyHostToDevice, st));
+        enc_hybrid_write(ha, st);
+        return PF_OK;
+    };
+    if (hyb && delta) {
+        const int rc = hybrid_sizes();
+        if (rc) return rc;
+    }
     if (delta) {
         // size pass -> scan -> page totals (one D2H, one sync) -> sections -> write pass
         DeltaArgs da{};
@@ -683,18 +749,45 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             dpages[i].out_off = take(vo, htot[i]);
             sections.push_back({dpages[i].out_off, htot[i]});
         }
+        if (hyb) place_levels(vo);
         HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
         da.out = static_cast<uint8_t*>(ctx->d_enc_sec.p);
         HIPCHK(ctx, hipMemcpyAsync(A + o_dpg, dpages.data(), sizeof(DeltaPage) * dpages.size(), hipMemcpyHostToDevice, st));
         enc_delta_write(ea, da, m, st);
+        if (hyb) {
+            const int rc = hybrid_write(da.out);
+            if (rc) return rc;
+        }
         HIPCHK(ctx, hipGetLastError());
         EVREC(ctx, ctx->ev[5], st);
     }
     uint8_t* SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
-    if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size
+    if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size (hybrid runs: after their size pass)
+        if (hyb) {
+            // The dictionary page and the ids are written before the size pass: room for the worst case of
+            // every section (an element is at most a 5-byte varint and the value, or a header and a group)
+            auto worst = [](uint64_t cnt, uint32_t b) { return (cnt / 8 + 1) * std::max<uint64_t>(b + 1, 5 + (b + 7) / 8); };
+            size_t ub = vo + 512 + sizeof(EncPage) * pp.size();
+            for (const PagePlanE& p : pp)
+                ub += 256 + size_t(dict ? 1 + worst(p.cnt, bw) : brle ? 4 + worst(p.cnt, 1) : p.plain) +
+                      size_t(col->max_def == 1 ? worst(uint64_t(p.r1 - p.r0), 1) : 0);
+            HIPCHK(ctx, ctx->d_enc_sec.ensure(ub));
+            ea.dict_out = static_cast<uint8_t*>(ctx->d_enc_sec.p) + o_dict;
+            const int rc = hybrid_sizes();
+            if (rc) return rc;
+        }
         for (size_t i = 0; i < pp.size(); i++) {
             const PagePlanE& p = pp[i];
             uint64_t bytes;
+            if (vs_of[i] >= 0) {   // width byte or 4-byte length, then the stream
+                const uint64_t pre = dict ? 1 : 4;
+                bytes = pre + hbytes[size_t(vs_of[i])];
+                ep[i] = EncPage{0, p.d0, p.cnt, dict ? 1u : 0u, bw};
+                ep[i].out_off = take(vo, bytes);
+                hs[size_t(vs_of[i])].out_off = ep[i].out_off + pre;
+                sections.push_back({ep[i].out_off, bytes});
+                continue;
+            }
             if (dict) {
                 const uint64_t groups = (p.cnt + 7) / 8;
                 bytes = p.cnt ? 1 + uvarint_len((groups << 1) | 1) + groups * bw : 1;
@@ -705,27 +798,35 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             ep[i].out_off = take(vo, bytes);
             sections.push_back({ep[i].out_off, bytes});
         }
+        if (hyb) place_levels(vo);
         const size_t o_pages = take(vo, sizeof(EncPage) * ep.size());
-        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
+        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));   // hybrid runs: within the worst case reserved above, nothing moves
         SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
         ea.dict_out = SEC + o_dict;
         ea.vals_out = SEC;
         EVREC(ctx, ctx->ev[4], st);
-        if (dict) enc_dictionary_page_and_ids(ea, m, st);
+        if (dict && !hyb) enc_dictionary_page_and_ids(ea, m, st);
         HIPCHK(ctx, hipMemcpyAsync(SEC + o_pages, ep.data(), sizeof(EncPage) * ep.size(), hipMemcpyHostToDevice, st));
-        enc_pages(ea, reinterpret_cast<const EncPage*>(SEC + o_pages), int(ep.size()), st);
+        if (!(hyb && (dict || brle))) enc_pages(ea, reinterpret_cast<const EncPage*>(SEC + o_pages), int(ep.size()), st);
+        if (hyb) {
+            const int rc = hybrid_write(SEC);
+            if (rc) return rc;
+        }
         HIPCHK(ctx, hipGetLastError());
         EVREC(ctx, ctx->ev[5], st);
     }
     std::vector<std::vector<uint8_t>> bodies;
+    std::vector<uint8_t> hlv(lv_total);   // hybrid runs: the pages' levels
     float snap_ms = 0.f;
     if (col->codec == PF_CODEC_SNAPPY) {
+        if (lv_total) HIPCHK(ctx, hipMemcpyAsync(hlv.data(), SEC + o_lv, lv_total, hipMemcpyDeviceToHost, st));
         const int rc = compress_sections(ctx, SEC, sections, bodies, &snap_ms);
         if (rc) return rc;
     } else {
         std::vector<uint8_t> all(vo);
         HIPCHK(ctx, hipMemcpyAsync(all.data(), SEC, vo, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
+        if (lv_total) std::memcpy(hlv.data(), all.data() + o_lv, lv_total);
         for (const auto& sct : sections) bodies.emplace_back(all.begin() + sct.first, all.begin() + sct.first + sct.second);
     }
 
@@ -754,7 +855,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         const PagePlanE& p = pp[i];
         const int64_t rows = p.r1 - p.r0;
         std::vector<uint8_t> def;
-        if (col->max_def == 1) {   // RLE/bit-packed hybrid, bit width 1: one bit-packed run = the validity bits
+        if (lv_of[i] >= 0) {       // hybrid runs: the stream the GPU encoded from the validity bits
+            def.assign(hlv.begin() + lv_off[i], hlv.begin() + lv_off[i] + hbytes[size_t(lv_of[i])]);
+        } else if (col->max_def == 1) {   // RLE/bit-packed hybrid, bit width 1: one bit-packed run = the validity bits
             const uint64_t groups = uint64_t(rows + 7) / 8;
             put_uvarint(def, (groups << 1) | 1);
             for (uint64_t g = 0; g < groups; g++) {

@@ -222,8 +222,9 @@ int pf_writer_close(pf_writer* w) {
                 // RLE_DICTIONARY ids; a DELTA_* chunk has no PLAIN page
                 const bool dict = c.data_encoding == PF_ENC_RLE_DICTIONARY;
                 const bool delta = c.data_encoding == PF_ENC_DELTA_BINARY_PACKED || c.data_encoding == PF_ENC_DELTA_BYTE_ARRAY;
-                t.list_header(2, T_I32, dict ? 3 : 2);
-                t.zigzag(delta ? c.data_encoding : PF_ENC_PLAIN);
+                const bool rle = c.data_encoding == PF_ENC_RLE;   // BOOLEAN values in the levels' encoding: RLE alone
+                t.list_header(2, T_I32, dict ? 3 : rle ? 1 : 2);
+                if (!rle) t.zigzag(delta ? c.data_encoding : PF_ENC_PLAIN);
                 t.zigzag(PF_ENC_RLE);
                 if (dict) t.zigzag(PF_ENC_RLE_DICTIONARY);
                 t.list_header(3, T_BINARY, 1);

@@ -14,10 +14,17 @@ dictionary-encoded is written as parquet-mr's v2 writer writes it: DELTA_BINARY_
 INT64) or DELTA_BYTE_ARRAY (BINARY) data pages, encoded on the GPU in parquet-mr's stream layout;
 FLOAT, DOUBLE and BOOLEAN stay PLAIN.
 
+With hybrid_runs=True (PF_ENCODE_HYBRID_RUNS) the RLE / bit-packed hybrid streams get the run shape of
+parquet-mr's RunLengthBitPackingHybridEncoder, encoded on the GPU: RLE runs of 8 or more repeats
+between bit-packed groups in the dictionary ids (width 0 for a one-entry dictionary) and in the
+definition levels of an OPTIONAL column, and BOOLEAN chunks in the RLE encoding. By default ids and
+levels are one bit-packed run per page and BOOLEAN is PLAIN. delta_fallback=True with
+hybrid_runs=True gives the encodings parquet-mr's PARQUET_2_0 writer gives.
+
 Differences that are allowed by the format and documented in DESIGN.md: the fallback is decided
 for the whole chunk (parquet-mr switches mid-chunk and also drops a dictionary that does not
-compress, isCompressionSatisfying), ids are written as one bit-packed run per page, no page /
-column statistics are written.
+compress, isCompressionSatisfying), ids are written as one bit-packed run per page unless
+hybrid_runs is set, no page / column statistics are written.
 """
 import ctypes as C
 
@@ -27,7 +34,7 @@ from . import _native
 from ._native import PfError, check, lib
 
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1, 2, 3, 4, 5, 6, 7
-ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK = 1, 2   # pf_encode_column.dictionary bits (PF_ENCODE_*)
+ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK, ENCODE_HYBRID_RUNS = 1, 2, 4   # pf_encode_column.dictionary bits (PF_ENCODE_*)
 _WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, FLOAT: 4, DOUBLE: 8}
 _DTYPE = {BOOLEAN: np.uint8, INT32: np.int32, INT64: np.int64, FLOAT: np.float32, DOUBLE: np.float64}
 _NAMES = {BOOLEAN: "BOOLEAN", INT32: "INT32", INT64: "INT64", INT96: "INT96", FLOAT: "FLOAT", DOUBLE: "DOUBLE",
@@ -179,9 +186,10 @@ class GpuColumnEncoder:
         self.dec = decoder
 
     def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1,
-               delta_fallback=False):
+               delta_fallback=False, hybrid_runs=False):
         """delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
-        dictionary-encoded (INT32, INT64, BINARY)."""
+        dictionary-encoded (INT32, INT64, BINARY). hybrid_runs: PF_ENCODE_HYBRID_RUNS, ids, definition
+        levels and BOOLEAN values as parquet-mr's hybrid encoder writes them (RLE runs and bit-packed groups)."""
         c = EncodeColumn()
         c.physical_type = field.physical_type
         c.max_def = 1 if field.optional else 0
@@ -205,7 +213,8 @@ class GpuColumnEncoder:
             v = np.ascontiguousarray(validity, np.uint8)
             keep.append(v)
             c.validity = v.ctypes.data
-        c.dictionary = (ENCODE_DICTIONARY if dictionary else 0) | (ENCODE_DELTA_FALLBACK if delta_fallback else 0)
+        c.dictionary = ((ENCODE_DICTIONARY if dictionary else 0) | (ENCODE_DELTA_FALLBACK if delta_fallback else 0) |
+                        (ENCODE_HYBRID_RUNS if hybrid_runs else 0))
         c.page_rows = page_rows
         c.dict_page_limit = dict_page_limit
         c.codec = codec
@@ -220,8 +229,9 @@ class ParquetWriter:
     block size; the bound here is in rows, the byte size of a row group is the caller's)."""
 
     def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=1,
-                 decoders=None, delta_fallback=False):
+                 decoders=None, delta_fallback=False, hybrid_runs=False):
         """delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
+        hybrid_runs: ids, definition levels and BOOLEAN values in parquet-mr's hybrid run shape (see above).
         decoders: several contexts (GpuDecoder) to encode the columns of a row group in parallel
         (one host thread each); chunks are still appended in schema order."""
         from .decoder import GpuDecoder
@@ -234,6 +244,7 @@ class ParquetWriter:
         self.kernel_ms = {"snappy": 0.0, "encode": 0.0, "snappy_in": 0, "snappy_out": 0}
         self.codec = codec
         self.delta_fallback = delta_fallback
+        self.hybrid_runs = hybrid_runs
         self.buf = _RowBuffer(schema)
         self.last_chunks = []     # (dict_entries, data_encoding, fallback) of the last row group
         fields = (WriteField * len(schema.fields))()
@@ -298,7 +309,8 @@ class ParquetWriter:
                             return
                         i = order.pop(0)
                     f, d, validity = work[i]
-                    out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback)
+                    out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
+                                     hybrid_runs=self.hybrid_runs)
                     keep = C.create_string_buffer(C.string_at(out.bytes, out.size), max(1, out.size))
                     cp = EncodedChunk.from_buffer_copy(out)
                     cp.bytes = C.cast(keep, C.c_void_p)
@@ -325,7 +337,8 @@ class ParquetWriter:
             raise PfError(rc, "pf_writer_add_chunk: " + (lib().pf_writer_last_error() or b"").decode(errors="replace"))
 
     def _encode_add(self, f, data, validity, n, i):
-        out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback)
+        out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
+                              hybrid_runs=self.hybrid_runs)
         self._add(out, i)
         return out
 
