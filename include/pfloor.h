@@ -311,6 +311,18 @@ const char* pf_file_created_by(pf_file* f);
                                         an OPTIONAL column whatever its values' encoding, and BOOLEAN values
                                         (PF_ENC_RLE: 4-byte length + stream). Clear: ids and levels are one
                                         bit-packed run per page, BOOLEAN is PLAIN */
+#define PF_ENCODE_STATISTICS     8   /* Statistics (null_count, min_value / max_value, the legacy min / max where
+                                        parquet-mr writes them) in every DataPageHeaderV2 and, through
+                                        pf_writer_add_chunk, in ColumnMetaData, reduced on the GPU over the
+                                        present values under ColumnOrder TYPE_ORDER: signed integers; NaN
+                                        skipped, a zero min written -0.0 and a zero max +0.0; BYTE_ARRAY
+                                        unsigned bytewise, untruncated; none when len(min) + len(max) >= 4096.
+                                        Clear: no statistics, the bytes of every release before it */
+#define PF_ENCODE_PAGE_CRC       16  /* PageHeader.crc (CRC-32 of the compressed_page_size bytes after the
+                                        header, dictionary pages included), its pieces reduced on the GPU.
+                                        Clear: no crc field */
+#define PF_STATS_NULL_COUNT 1        /* pf_encoded_chunk.stats_flags: null_count is set */
+#define PF_STATS_MIN_MAX    2        /* stat_min / stat_max are set */
 typedef struct pf_encode_column {
     int32_t  physical_type;       /* PF_BOOLEAN, PF_INT32, PF_INT64, PF_FLOAT, PF_DOUBLE, PF_BYTE_ARRAY */
     int32_t  max_def;             /* 0 = REQUIRED, 1 = OPTIONAL */
@@ -322,7 +334,8 @@ typedef struct pf_encode_column {
     int64_t  chars_len;
     int32_t  dictionary;          /* PF_ENCODE_* bits; 1: dictionary-encode (PLAIN above dict_page_limit or on a
                                      hash collision), 3: the same with the DELTA_* fallback, 2: DELTA_* pages;
-                                     | 4: parquet-mr's hybrid runs (7 = the encodings of its PARQUET_2_0 writer) */
+                                     | 4: parquet-mr's hybrid runs (7 = the encodings of its PARQUET_2_0 writer);
+                                     | 8: statistics; | 16: page CRCs */
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
     int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's) or PF_CODEC_UNCOMPRESSED */
@@ -346,6 +359,13 @@ typedef struct pf_encoded_chunk {
     float    snappy_ms;           /* k_snappy_compress time (HIP events; 0 when stage timing is off) */
     float    encode_ms;           /* dictionary + page (PLAIN, ids, DELTA_*, hybrid runs) kernels time (HIP events; 0 when timing is off) */
     int64_t  snappy_in, snappy_out;    /* bytes into / out of the compressor */
+    /* Chunk statistics (PF_ENCODE_STATISTICS; all zero: none). pf_writer_add_chunk writes them as
+     * ColumnMetaData.statistics, and a file with any gets FileMetaData.column_orders (TYPE_ORDER). */
+    int32_t  stats_flags;         /* PF_STATS_* */
+    int32_t  stat_min_len, stat_max_len;
+    int64_t  null_count;
+    const uint8_t* stat_min;      /* PLAIN bytes of the min / max (BYTE_ARRAY: no length prefix); owned by the ctx, */
+    const uint8_t* stat_max;      /* valid until its next pf_encode_chunk, like bytes */
 } pf_encoded_chunk;
 
 /* Encode one column chunk on the context's GPU. Inputs are host memory (copied) unless

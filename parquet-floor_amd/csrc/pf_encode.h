@@ -116,6 +116,46 @@ struct HybridArgs {
 hipError_t enc_hybrid_sizes(const HybridArgs& t, hipStream_t st);
 void enc_hybrid_write(const HybridArgs& t, hipStream_t st);
 
+// ---- page and chunk statistics (pf_enc_stats.hip; PF_ENCODE_STATISTICS) ----
+constexpr uint32_t ST_TILE = 4096;    // dense values of one workgroup
+constexpr uint32_t ST_LIMIT = 4096;   // len(min) + len(max) at or above it: no Statistics struct
+
+struct StatTile {
+    uint32_t page, d0, cnt, pad;      // dense values [d0, d0 + cnt) of data page `page`
+};
+
+// A tile's partial, a page's result and the chunk's. Partials hold keys; results hold the PLAIN bits of a
+// fixed-width min / max, or for strings the winners' dense indices and lengths.
+struct StatPart {
+    uint64_t mn, mx;
+    uint32_t mnl, mxl;                // strings: min(len, 8) beside a key, the full length in a result
+    uint32_t mni, mxi;                // strings: dense index of the winner
+    uint32_t any, pad;                // 0: no value (FLOAT / DOUBLE: none that is not NaN); 1: min / max; 2: over ST_LIMIT
+};
+
+struct StatArgs {
+    const StatTile* tiles;           // n_tiles, in page order
+    const uint32_t* ptile;           // n_pages + 1: page p owns tiles [ptile[p], ptile[p + 1])
+    uint32_t n_tiles, n_pages;
+    StatPart* part;                  // n_tiles
+    uint32_t* win;                   // strings, 2 x n_tiles: a tile's winners among the values with the page's extreme keys
+    StatPart* out;                   // n_pages + 1: the pages, then the chunk
+    uint8_t* bytes;                  // strings, (n_pages + 1) x ST_LIMIT: min ‖ max of every entry with any == 1
+};
+
+void enc_stats(const EncArgs& a, const StatArgs& s, hipStream_t st);
+
+// ---- page CRCs (pf_enc_crc.hip; PF_ENCODE_PAGE_CRC) ----
+struct CrcPiece {
+    const uint8_t* ptr;
+    const uint32_t* len_ptr;         // the length in device memory (a compression job's), or nullptr: `len`
+    uint32_t len, cap;               // cap: bytes readable at ptr
+};
+struct CrcOut {
+    uint32_t raw, len, x8len, pad;   // raw CRC (zero init, no final xor), bytes, x^(8 len) mod P
+};
+void launch_enc_crc(const CrcPiece* d_pieces, int n_pieces, CrcOut* d_out, hipStream_t st);
+
 hipError_t enc_scan_temp(size_t n, size_t& bytes);
 hipError_t enc_dense(const EncArgs& a, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t enc_plain_sizes(const EncArgs& a, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);

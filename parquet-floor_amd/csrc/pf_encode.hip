@@ -12,6 +12,8 @@
 //                   validity bits themselves, written by the host; DELTA_BINARY_PACKED /
 //                   DELTA_BYTE_ARRAY values sections: pf_enc_delta.hip; ids, levels and BOOLEAN values
 //                   in parquet-mr's run shape (PF_ENCODE_HYBRID_RUNS): pf_enc_hybrid.hip
+//   statistics   -> min / max of every page and of the chunk over the dense values (PF_ENCODE_STATISTICS):
+//                   pf_enc_stats.hip; PageHeader.crc from the stored pieces (PF_ENCODE_PAGE_CRC): pf_enc_crc.hip
 //   Snappy       -> k_snappy_compress: one wave per 8 KiB job (hash table of 4-byte
 //                   prefixes in LDS, 64 candidate positions per step, wave-parallel match
 //                   extension); jobs are independent, so a page's stream is the varint length

@@ -50,11 +50,23 @@ struct FileMeta {
     static void walk_pages(const uint8_t* chunk, size_t size, const ChunkMeta& m, std::vector<pf_page_desc>& out);
 };
 
+// Statistics of a page or a chunk as the write path serialises them (parquet.thrift Statistics: 3 null_count,
+// 5 max_value, 6 min_value; the legacy 1 max / 2 min only where `legacy` says so).
+struct StatsOut {
+    bool present = false;      // write the struct at all
+    bool has_min_max = false, legacy = false;
+    int64_t null_count = 0;
+    std::string min, max;      // PLAIN bytes
+};
+
 // One page header of the write path (pf_write.cpp serialises it as a Thrift compact PageHeader).
 struct PageHeaderOut {
     int32_t page_type = 0, uncompressed_size = 0, compressed_size = 0;
     int32_t num_values = 0, num_nulls = 0, num_rows = 0, encoding = 0, def_bytes = 0;
     bool is_compressed = true;
+    bool has_crc = false;
+    uint32_t crc = 0;          // PageHeader.crc (field 4): CRC-32 of the compressed_size bytes after the header
+    StatsOut stats;            // DataPageHeaderV2.statistics (field 8)
 };
 void write_page_header(std::vector<uint8_t>& out, const PageHeaderOut& h);
 

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "pf_crc.h"
 #include "pf_encode.h"
 #include "pf_host.h"
 #include "pf_launch.h"
@@ -170,6 +171,8 @@ struct pf_ctx {
     DevBuf d_scan_in, d_scan;              // pf_scan_pages: host chunk bytes, tables
     DevBuf d_enc, d_enc_sec, d_enc_out;    // pf_encode_chunk / pf_snappy_compress: work arena, values sections, slots
     std::vector<uint8_t> h_enc;            // the last encoded chunk (headers + bodies)
+    std::vector<uint8_t> h_enc_stat;       // its chunk statistics (min ‖ max)
+    HostBuf h_enc_st;                      // pf_encode_chunk: statistics results D2H
     HostBuf h_meta, h_res;
     HostBuf h_enc_slots;                   // pf_encode_chunk / pf_snappy_compress: compressed slots D2H
     // last batch
@@ -399,8 +402,11 @@ void put_uvarint(std::vector<uint8_t>& o, uint64_t v) {
 
 // Snappy-compress `sections` (device, each [off, off + len) of `base`) into SC_BLOCK-job slots;
 // returns per section the host stream (varint length + block outputs) in `streams`.
+// With `crc_out` (PF_ENCODE_PAGE_CRC): k_enc_crc right behind the compressor over every job's slot, in job
+// order, then over `extra`; the results come back in the copy that brings the jobs' lengths.
 int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::pair<uint64_t, uint64_t>>& sections,
-                      std::vector<std::vector<uint8_t>>& streams, float* kernel_ms = nullptr) {
+                      std::vector<std::vector<uint8_t>>& streams, float* kernel_ms = nullptr,
+                      const std::vector<CrcPiece>* extra = nullptr, std::vector<CrcOut>* crc_out = nullptr, float* crc_ms = nullptr) {
     hipStream_t st = ctx->stream;
     std::vector<SnapCJob> jobs;
     std::vector<std::pair<size_t, size_t>> range(sections.size());   // jobs of each section
@@ -418,25 +424,49 @@ int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::p
     size_t m = 0;
     auto take = [](size_t& cur, size_t sz) { size_t o = align_up(cur, 256); cur = o + sz; return o; };
     const size_t o_jobs = take(m, sizeof(SnapCJob) * std::max<size_t>(nj, 1));
-    const size_t o_len = take(m, 4 * std::max<size_t>(nj, 1));
+    // the jobs' lengths and, behind them, the pieces' CRCs: one D2H
+    const size_t np = crc_out ? nj + (extra ? extra->size() : 0) : 0;
+    const size_t o_crc_in_len = align_up(4 * nj, 16);
+    const size_t len_bytes = np ? o_crc_in_len + sizeof(CrcOut) * np : 4 * std::max<size_t>(nj, 1);
+    const size_t o_len = take(m, len_bytes);
+    const size_t o_pieces = take(m, sizeof(CrcPiece) * std::max<size_t>(np, 1));
     const size_t o_slots = take(m, size_t(SC_SLOT) * std::max<size_t>(nj, 1));
     HIPCHK(ctx, ctx->d_enc_out.ensure(m));
     uint8_t* d = static_cast<uint8_t*>(ctx->d_enc_out.p);
     for (size_t k = 0; k < nj; k++) jobs[k].dst = d + o_slots + k * SC_SLOT;
     // compressed lengths + slots come back into the context's pinned staging (no zero-fill, DMA speed)
-    HIPCHK(ctx, ctx->h_enc_slots.ensure(align_up(4 * std::max<size_t>(nj, 1), 256) + nj * size_t(SC_SLOT)));
+    HIPCHK(ctx, ctx->h_enc_slots.ensure(align_up(len_bytes, 256) + nj * size_t(SC_SLOT)));
     uint32_t* lens = static_cast<uint32_t*>(ctx->h_enc_slots.p);
-    uint8_t* slots = static_cast<uint8_t*>(ctx->h_enc_slots.p) + align_up(4 * std::max<size_t>(nj, 1), 256);
+    uint8_t* slots = static_cast<uint8_t*>(ctx->h_enc_slots.p) + align_up(len_bytes, 256);
+    std::vector<CrcPiece> pieces(np);
     if (nj) {
         HIPCHK(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(SnapCJob) * nj, hipMemcpyHostToDevice, st));
         EVREC(ctx, ctx->ev[0], st);
         launch_snappy_compress(reinterpret_cast<const SnapCJob*>(d + o_jobs), int(nj), reinterpret_cast<uint32_t*>(d + o_len), st);
         HIPCHK(ctx, hipGetLastError());
         EVREC(ctx, ctx->ev[1], st);
-        HIPCHK(ctx, hipMemcpyAsync(lens, d + o_len, 4 * nj, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(slots, d + o_slots, nj * size_t(SC_SLOT), hipMemcpyDeviceToHost, st));
     }
+    if (np) {
+        const uint32_t* d_len = reinterpret_cast<const uint32_t*>(d + o_len);
+        for (size_t k = 0; k < nj; k++) pieces[k] = CrcPiece{jobs[k].dst, d_len + k, 0u, SC_SLOT};
+        for (size_t k = nj; k < np; k++) pieces[k] = (*extra)[k - nj];
+        HIPCHK(ctx, hipMemcpyAsync(d + o_pieces, pieces.data(), sizeof(CrcPiece) * np, hipMemcpyHostToDevice, st));
+        EVREC(ctx, ctx->ev[8], st);
+        launch_enc_crc(reinterpret_cast<const CrcPiece*>(d + o_pieces), int(np), reinterpret_cast<CrcOut*>(d + o_len + o_crc_in_len), st);
+        HIPCHK(ctx, hipGetLastError());
+        EVREC(ctx, ctx->ev[9], st);
+    }
+    if (nj || np) HIPCHK(ctx, hipMemcpyAsync(lens, d + o_len, np ? len_bytes : 4 * nj, hipMemcpyDeviceToHost, st));
+    if (nj) HIPCHK(ctx, hipMemcpyAsync(slots, d + o_slots, nj * size_t(SC_SLOT), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    if (crc_out) {
+        const CrcOut* h = reinterpret_cast<const CrcOut*>(reinterpret_cast<const uint8_t*>(lens) + o_crc_in_len);
+        crc_out->assign(h, h + np);
+    }
+    if (crc_ms) {
+        *crc_ms = 0.f;
+        if (ctx->timing && np) HIPCHK(ctx, hipEventElapsedTime(crc_ms, ctx->ev[8], ctx->ev[9]));
+    }
     if (kernel_ms) {
         *kernel_ms = 0.f;
         if (ctx->timing && nj) HIPCHK(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]));
@@ -558,6 +588,20 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     // ids or BOOLEAN values
     const bool hyb = (col->dictionary & PF_ENCODE_HYBRID_RUNS) != 0;
     const size_t n_hs_max = hyb ? 2 * pp.size() : 0;
+    // statistics (PF_ENCODE_STATISTICS): a workgroup per (page, tile of ST_TILE present values)
+    const bool want_stats = (col->dictionary & PF_ENCODE_STATISTICS) != 0;
+    const bool want_crc = (col->dictionary & PF_ENCODE_PAGE_CRC) != 0;
+    std::vector<StatTile> stiles;
+    std::vector<uint32_t> sptile;
+    if (want_stats) {
+        for (size_t i = 0; i < pp.size(); i++) {
+            sptile.push_back(uint32_t(stiles.size()));
+            for (uint32_t o = 0; o < pp[i].cnt; o += ST_TILE)
+                stiles.push_back(StatTile{uint32_t(i), pp[i].d0 + o, std::min(ST_TILE, pp[i].cnt - o), 0u});
+        }
+        sptile.push_back(uint32_t(stiles.size()));
+    }
+    const size_t n_se = want_stats ? pp.size() + 1 : 0;   // statistics entries: the pages, then the chunk
 
     // ---- device arena ----
     size_t a_sz = 0;
@@ -580,6 +624,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     const size_t o_dby = take(a_sz, 4 * NI1), o_dof = take(a_sz, 4 * NI1), o_dmin = take(a_sz, 8 * NI1), o_dwd = take(a_sz, 4 * NI1);
     const size_t o_dtot = take(a_sz, 4 * dpages.size());
     const size_t o_hstr = take(a_sz, sizeof(HybridStream) * n_hs_max), o_hby = take(a_sz, 4 * n_hs_max);
+    const size_t o_stt = take(a_sz, sizeof(StatTile) * stiles.size()), o_stp = take(a_sz, 4 * sptile.size());
+    const size_t o_spart = take(a_sz, sizeof(StatPart) * stiles.size()), o_swin = take(a_sz, str ? 8 * stiles.size() : 0);
+    const size_t o_sout = take(a_sz, sizeof(StatPart) * n_se), o_sbytes = take(a_sz, str ? size_t(ST_LIMIT) * n_se : 0);
     size_t temp_bytes = 0;
     HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
     const size_t o_temp = take(a_sz, temp_bytes);
@@ -713,6 +760,31 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         enc_hybrid_write(ha, st);
         return PF_OK;
     };
+    // Statistics: the kernels run with the page kernels (their time is in encode_ms), the results come back in
+    // pinned memory with the synchronisation the bodies wait for anyway.
+    const size_t st_bytes = sizeof(StatPart) * n_se + (str ? size_t(ST_LIMIT) * n_se : 0);
+    auto stats_launch = [&]() -> int {
+        if (!want_stats) return PF_OK;
+        StatArgs sa{};
+        sa.tiles = reinterpret_cast<const StatTile*>(A + o_stt); sa.ptile = reinterpret_cast<const uint32_t*>(A + o_stp);
+        sa.n_tiles = uint32_t(stiles.size()); sa.n_pages = uint32_t(pp.size());
+        sa.part = reinterpret_cast<StatPart*>(A + o_spart); sa.win = reinterpret_cast<uint32_t*>(A + o_swin);
+        sa.out = reinterpret_cast<StatPart*>(A + o_sout); sa.bytes = A + o_sbytes;
+        if (!stiles.empty())
+            HIPCHK(ctx, hipMemcpyAsync(A + o_stt, stiles.data(), sizeof(StatTile) * stiles.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(A + o_stp, sptile.data(), 4 * sptile.size(), hipMemcpyHostToDevice, st));
+        enc_stats(ea, sa, st);
+        HIPCHK(ctx, hipGetLastError());
+        return PF_OK;
+    };
+    auto stats_fetch = [&]() -> int {
+        if (!want_stats) return PF_OK;
+        HIPCHK(ctx, ctx->h_enc_st.ensure(st_bytes));
+        uint8_t* h = static_cast<uint8_t*>(ctx->h_enc_st.p);
+        HIPCHK(ctx, hipMemcpyAsync(h, A + o_sout, sizeof(StatPart) * n_se, hipMemcpyDeviceToHost, st));
+        if (str) HIPCHK(ctx, hipMemcpyAsync(h + sizeof(StatPart) * n_se, A + o_sbytes, size_t(ST_LIMIT) * n_se, hipMemcpyDeviceToHost, st));
+        return PF_OK;
+    };
     if (hyb && delta) {
         const int rc = hybrid_sizes();
         if (rc) return rc;
@@ -759,7 +831,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             if (rc) return rc;
         }
         HIPCHK(ctx, hipGetLastError());
+        if (const int rc = stats_launch()) return rc;
         EVREC(ctx, ctx->ev[5], st);
+        if (const int rc = stats_fetch()) return rc;
     }
     uint8_t* SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
     if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size (hybrid runs: after their size pass)
@@ -813,19 +887,63 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             if (rc) return rc;
         }
         HIPCHK(ctx, hipGetLastError());
+        if (const int rc = stats_launch()) return rc;
         EVREC(ctx, ctx->ev[5], st);
+        if (const int rc = stats_fetch()) return rc;
     }
     std::vector<std::vector<uint8_t>> bodies;
     std::vector<uint8_t> hlv(lv_total);   // hybrid runs: the pages' levels
-    float snap_ms = 0.f;
+    float snap_ms = 0.f, crc_ms = 0.f;
+    // Page CRCs (PF_ENCODE_PAGE_CRC): the pieces of the pages that lie in device memory -- the compression jobs'
+    // slots (SNAPPY; compress_sections lists them) or the sections themselves, and the levels: the stream the GPU
+    // encoded (hybrid runs), or the whole validity bytes of the page's rows, which the one bit-packed run repeats
+    // -- go through k_enc_crc; `crcs` holds the jobs (SNAPPY) or sections first, then the levels.
+    std::vector<CrcPiece> lv_pieces;
+    std::vector<CrcOut> crcs;
+    std::vector<int> lv_piece(pp.size(), -1);   // the page's whole level stream
+    std::vector<int> vb_piece(pp.size(), -1);   // the whole bytes of its bit-packed run, between header and last partial byte
+    if (want_crc)
+        for (size_t i = 0; i < pp.size(); i++) {
+            if (lv_of[i] >= 0) {
+                const uint32_t nb = hbytes[size_t(lv_of[i])];
+                lv_piece[i] = int(lv_pieces.size());
+                lv_pieces.push_back(CrcPiece{SEC + o_lv + lv_off[i], nullptr, nb, nb});
+            } else if (has_val && pp[i].r1 - pp[i].r0 >= 8) {   // (pages start on a validity byte)
+                const uint32_t nb = uint32_t((pp[i].r1 - pp[i].r0) / 8);
+                vb_piece[i] = int(lv_pieces.size());
+                lv_pieces.push_back(CrcPiece{ea.validity + pp[i].r0 / 8, nullptr, nb, nb});
+            }
+        }
+    size_t crc_first_lv = 0;   // index of the first level stream in crcs
     if (col->codec == PF_CODEC_SNAPPY) {
         if (lv_total) HIPCHK(ctx, hipMemcpyAsync(hlv.data(), SEC + o_lv, lv_total, hipMemcpyDeviceToHost, st));
-        const int rc = compress_sections(ctx, SEC, sections, bodies, &snap_ms);
+        const int rc = compress_sections(ctx, SEC, sections, bodies, &snap_ms, &lv_pieces, want_crc ? &crcs : nullptr, &crc_ms);
         if (rc) return rc;
+        if (want_crc) crc_first_lv = crcs.size() - lv_pieces.size();
     } else {
+        std::vector<CrcPiece> pieces;   // (alive until the synchronisation below: the upload reads it)
+        if (want_crc) {   // the table and the results in d_enc_out, which an uncompressed chunk does not use otherwise
+            for (const auto& sct : sections) {
+                if (sct.second > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
+                pieces.push_back(CrcPiece{SEC + sct.first, nullptr, uint32_t(sct.second), uint32_t(sct.second)});
+            }
+            crc_first_lv = pieces.size();
+            pieces.insert(pieces.end(), lv_pieces.begin(), lv_pieces.end());
+            const size_t npc = pieces.size(), o_res = align_up(sizeof(CrcPiece) * npc, 256);
+            HIPCHK(ctx, ctx->d_enc_out.ensure(o_res + sizeof(CrcOut) * npc));
+            uint8_t* d = static_cast<uint8_t*>(ctx->d_enc_out.p);
+            crcs.resize(npc);
+            HIPCHK(ctx, hipMemcpyAsync(d, pieces.data(), sizeof(CrcPiece) * npc, hipMemcpyHostToDevice, st));
+            EVREC(ctx, ctx->ev[8], st);
+            launch_enc_crc(reinterpret_cast<const CrcPiece*>(d), int(npc), reinterpret_cast<CrcOut*>(d + o_res), st);
+            HIPCHK(ctx, hipGetLastError());
+            EVREC(ctx, ctx->ev[9], st);
+            HIPCHK(ctx, hipMemcpyAsync(crcs.data(), d + o_res, sizeof(CrcOut) * npc, hipMemcpyDeviceToHost, st));
+        }
         std::vector<uint8_t> all(vo);
         HIPCHK(ctx, hipMemcpyAsync(all.data(), SEC, vo, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
+        if (want_crc && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&crc_ms, ctx->ev[8], ctx->ev[9]));
         if (lv_total) std::memcpy(hlv.data(), all.data() + o_lv, lv_total);
         for (const auto& sct : sections) bodies.emplace_back(all.begin() + sct.first, all.begin() + sct.first + sct.second);
     }
@@ -835,6 +953,60 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     o.clear();
     int64_t unc = 0;
     size_t bi = 0;
+    // CRC of a page: its pieces folded in stored order (pf_crc.h); the bytes the host generates itself (the
+    // length varint, a bit-packed level run built from hval) are fed bytewise.
+    size_t crc_job = 0;   // SNAPPY: the next job in crcs
+    bool crc_bad = false;
+    auto page_crc = [&](size_t sec, size_t page, const std::vector<uint8_t>& def) {
+        uint32_t raw = 0;
+        uint64_t len = 0;
+        auto piece = [&](const CrcOut& c) { raw = crc_combine_pow(raw, c.raw, c.x8len); len += c.len; };
+        if (page != size_t(-1) && lv_piece[page] >= 0) {
+            piece(crcs[crc_first_lv + size_t(lv_piece[page])]);
+        } else if (page != size_t(-1) && vb_piece[page] >= 0) {   // run header ‖ whole validity bytes (device) ‖ last partial byte
+            const CrcOut& c = crcs[crc_first_lv + size_t(vb_piece[page])];
+            const size_t groups = size_t(pp[page].r1 - pp[page].r0 + 7) / 8, hdr = def.size() - groups;
+            raw = crc_raw_bytes(raw, def.data(), hdr);
+            len += hdr;
+            piece(c);
+            raw = crc_raw_bytes(raw, def.data() + hdr + c.len, def.size() - hdr - c.len);
+            len += def.size() - hdr - c.len;
+        } else {
+            raw = crc_raw_bytes(raw, def.data(), def.size());
+            len += def.size();
+        }
+        if (col->codec == PF_CODEC_SNAPPY) {
+            const size_t vl = uvarint_len(sections[sec].second);
+            raw = crc_raw_bytes(raw, bodies[sec].data(), vl);
+            len += vl;
+            for (uint64_t o = 0; o < sections[sec].second; o += SC_BLOCK) piece(crcs[crc_job++]);
+        } else {
+            piece(crcs[sec]);
+        }
+        if (len != def.size() + bodies[sec].size()) crc_bad = true;   // the pieces are not the page
+        return crc_finish(raw, len);
+    };
+    // Statistics of entry e (a page, or pp.size(): the chunk) from the kernels' results
+    const StatPart* hst = want_stats ? static_cast<const StatPart*>(ctx->h_enc_st.p) : nullptr;
+    const uint8_t* hsb = want_stats ? static_cast<const uint8_t*>(ctx->h_enc_st.p) + sizeof(StatPart) * n_se : nullptr;
+    auto stats_of = [&](size_t e, int64_t nulls) {
+        StatsOut so;
+        if (!want_stats || hst[e].any == 2) return so;   // over the size limit: no struct at all
+        so.present = true;
+        so.null_count = nulls;
+        if (hst[e].any != 1) return so;
+        so.has_min_max = true;
+        if (str) {
+            const char* b = reinterpret_cast<const char*>(hsb + e * size_t(ST_LIMIT));
+            so.min.assign(b, hst[e].mnl);
+            so.max.assign(b + hst[e].mnl, hst[e].mxl);
+        } else {   // PLAIN: little-endian, w bytes (BOOLEAN: one byte)
+            so.min.assign(reinterpret_cast<const char*>(&hst[e].mn), size_t(w));
+            so.max.assign(reinterpret_cast<const char*>(&hst[e].mx), size_t(w));
+        }
+        so.legacy = !str || so.min == so.max;   // parquet-mr: the legacy fields only where the signed order is the type's
+        return so;
+    };
     out->dictionary_page_offset = -1;
     if (dict) {
         PageHeaderOut h;
@@ -843,6 +1015,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         h.compressed_size = int32_t(bodies[0].size());
         h.num_values = int32_t(D);
         h.encoding = PF_ENC_PLAIN;   // parquet-mr PARQUET_2_0: dictionary page PLAIN, data pages RLE_DICTIONARY
+        if (want_crc) { h.has_crc = true; h.crc = page_crc(0, size_t(-1), {}); }
         out->dictionary_page_offset = 0;
         const size_t h0 = o.size();
         write_page_header(o, h);
@@ -878,11 +1051,33 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         h.encoding = data_enc;
         h.def_bytes = int32_t(def.size());
         h.is_compressed = col->codec == PF_CODEC_SNAPPY;
+        if (want_crc) { h.has_crc = true; h.crc = page_crc(bi, i, def); }
+        h.stats = stats_of(i, rows - p.cnt);
         const size_t h0 = o.size();
         write_page_header(o, h);
         unc += int64_t(o.size() - h0) + h.uncompressed_size;
         o.insert(o.end(), def.begin(), def.end());
         o.insert(o.end(), bodies[bi].begin(), bodies[bi].end());
+    }
+    if (crc_bad) return fail(ctx, PF_ERR_HIP, "encode: the CRC pieces of a page do not add up to its size");
+    out->stats_flags = 0;
+    out->stat_min_len = out->stat_max_len = 0;
+    out->null_count = 0;
+    out->stat_min = out->stat_max = nullptr;
+    if (want_stats) {
+        const StatsOut so = stats_of(pp.size(), n - int64_t(m));
+        std::vector<uint8_t>& hb = ctx->h_enc_stat;
+        hb.assign(so.min.begin(), so.min.end());
+        hb.insert(hb.end(), so.max.begin(), so.max.end());
+        hb.push_back(0);   // never empty: the pointers below are not null
+        if (so.present) { out->stats_flags |= PF_STATS_NULL_COUNT; out->null_count = so.null_count; }
+        if (so.has_min_max) {
+            out->stats_flags |= PF_STATS_MIN_MAX;
+            out->stat_min_len = int32_t(so.min.size());
+            out->stat_max_len = int32_t(so.max.size());
+            out->stat_min = hb.data();
+            out->stat_max = hb.data() + so.min.size();
+        }
     }
     out->bytes = o.data();
     out->size = int64_t(o.size());
@@ -896,7 +1091,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     if (ctx->timing) {   // the page kernels' events have completed (the stream was synchronised since)
         float pg_ms = 0.f;
         HIPCHK(ctx, hipEventElapsedTime(&pg_ms, ctx->ev[4], ctx->ev[5]));
-        enc_ms += pg_ms;
+        enc_ms += pg_ms + crc_ms;
     }
     out->snappy_ms = snap_ms;
     out->encode_ms = enc_ms;
@@ -1031,6 +1226,7 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_meta.release();
     ctx->h_res.release();
     ctx->h_enc_slots.release();
+    ctx->h_enc_st.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);

@@ -20,6 +20,7 @@
 //                page's standard CRC32 (zlib / java.util.zip.CRC32).
 #include <hip/hip_runtime.h>
 
+#include "pf_crc.h"
 #include "pf_device.h"
 #include "pf_internal.h"
 #include "pf_launch.h"
@@ -246,31 +247,7 @@ __global__ __launch_bounds__(64) void k_page_scan(const ScanChunk* __restrict__ 
     if (lane == 0) res[c] = ScanResult{np, status, err_page, 0};
 }
 
-// ---- CRC32 (reflected polynomial 0xEDB88320, as zlib / java.util.zip.CRC32)
-constexpr uint32_t CRC_POLY = 0xedb88320u;
-
-// a * b mod P in the reflected representation (x^0 = bit 31).
-__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (uint32_t m = 1u << 31; m; m >>= 1) {
-        if (a & m) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8n) mod P from x2n[k] = x^(2^k) mod P.
-__device__ uint32_t crc_x8n(uint64_t n, const uint32_t* x2n) {
-    uint32_t p = 1u << 31;
-    unsigned k = 3;
-    while (n) {
-        if (n & 1) p = crc_mulmod(x2n[k & 31], p);
-        n >>= 1;
-        k++;
-    }
-    return p;
-}
-
+// ---- CRC32 (reflected polynomial 0xEDB88320, as zlib / java.util.zip.CRC32): arithmetic in pf_crc.h
 constexpr int CRC_NT = 256;
 
 __global__ __launch_bounds__(CRC_NT) void k_page_crc(const ScanCrc* __restrict__ crcs, const int* __restrict__ list,

@@ -51,15 +51,27 @@ struct ThriftWriter {
     void stop() { out.push_back(0); }
 };
 
-// PageHeader (parquet.thrift): 1 type, 2 uncompressed_page_size, 3 compressed_page_size,
+namespace {
+// Statistics (parquet.thrift): 1 max, 2 min (legacy, signed order), 3 null_count, 5 max_value, 6 min_value.
+void write_statistics(ThriftWriter& w, int id, const StatsOut& s) {
+    w.begin_struct(id);
+    if (s.has_min_max && s.legacy) { w.binary(1, s.max); w.binary(2, s.min); }
+    w.i64(3, s.null_count);
+    if (s.has_min_max) { w.binary(5, s.max); w.binary(6, s.min); }
+    w.end_struct();
+}
+}  // namespace
+
+// PageHeader (parquet.thrift): 1 type, 2 uncompressed_page_size, 3 compressed_page_size, 4 crc (optional),
 // 7 dictionary_page_header {1 num_values, 2 encoding}, 8 data_page_header_v2 {1 num_values,
 // 2 num_nulls, 3 num_rows, 4 encoding, 5 definition_levels_byte_length,
-// 6 repetition_levels_byte_length, 7 is_compressed}.
+// 6 repetition_levels_byte_length, 7 is_compressed, 8 statistics (optional)}.
 void write_page_header(std::vector<uint8_t>& out, const PageHeaderOut& h) {
     ThriftWriter w(out);
     w.i32(1, h.page_type);
     w.i32(2, h.uncompressed_size);
     w.i32(3, h.compressed_size);
+    if (h.has_crc) w.i32(4, int32_t(h.crc));   // the uint32 as the i32 the format declares
     if (h.page_type == PF_PAGE_DICTIONARY) {
         w.begin_struct(7);
         w.i32(1, h.num_values);
@@ -74,6 +86,7 @@ void write_page_header(std::vector<uint8_t>& out, const PageHeaderOut& h) {
         w.i32(5, h.def_bytes);
         w.i32(6, 0);
         w.boolean(7, h.is_compressed);
+        if (h.stats.present) write_statistics(w, 8, h.stats);
         w.end_struct();
     }
     w.stop();
@@ -90,6 +103,7 @@ int werr(int code, const std::string& m) { w_err = m; return code; }
 struct ChunkRec {
     int64_t file_offset = 0, size = 0, uncompressed = 0, num_values = 0, dict_offset = -1, data_offset = 0;
     int32_t data_encoding = 0, codec = 0;
+    StatsOut stats;
 };
 struct RowGroupRec {
     int64_t num_rows = 0;
@@ -105,6 +119,7 @@ struct pf_writer {
     std::vector<RowGroupRec> groups;
     RowGroupRec cur;
     bool failed = false;
+    bool any_stats = false;   // a chunk carried statistics: the footer declares column_orders
 };
 
 namespace {
@@ -154,8 +169,22 @@ int pf_writer_add_chunk(pf_writer* w, int field, const pf_encoded_chunk* c) {
     r.data_offset = w->pos + c->data_page_offset;
     r.data_encoding = c->data_encoding;
     r.codec = c->codec;
+    if (c->stats_flags & PF_STATS_MIN_MAX) {
+        if (!c->stat_min || !c->stat_max || c->stat_min_len < 0 || c->stat_max_len < 0)
+            return werr(PF_ERR_INVALID_ARG, "chunk statistics: min / max flagged but missing");
+        r.stats.has_min_max = true;
+        r.stats.min.assign(reinterpret_cast<const char*>(c->stat_min), size_t(c->stat_min_len));
+        r.stats.max.assign(reinterpret_cast<const char*>(c->stat_max), size_t(c->stat_max_len));
+        // the legacy fields: every type whose signed order is its TYPE_ORDER; BYTE_ARRAY only when min == max
+        r.stats.legacy = w->fields[size_t(field)].physical_type != PF_BYTE_ARRAY || r.stats.min == r.stats.max;
+    }
+    if (c->stats_flags & (PF_STATS_NULL_COUNT | PF_STATS_MIN_MAX)) {
+        r.stats.present = true;
+        r.stats.null_count = c->null_count;
+    }
     int rc = put(w, c->bytes, size_t(c->size));
     if (rc) return rc;
+    if (r.stats.present) w->any_stats = true;
     w->cur.chunks.push_back(r);
     return PF_OK;
 }
@@ -171,7 +200,7 @@ int pf_writer_end_row_group(pf_writer* w, int64_t num_rows) {
     return PF_OK;
 }
 
-// FileMetaData: 1 version, 2 schema, 3 num_rows, 4 row_groups, 6 created_by.
+// FileMetaData: 1 version, 2 schema, 3 num_rows, 4 row_groups, 6 created_by, 7 column_orders (only with statistics).
 int pf_writer_close(pf_writer* w) {
     if (!w) return werr(PF_ERR_INVALID_ARG, "null writer");
     int rc = PF_OK;
@@ -236,6 +265,7 @@ int pf_writer_close(pf_writer* w) {
                 t.i64(7, c.size);
                 t.i64(9, c.data_offset);
                 if (c.dict_offset >= 0) t.i64(11, c.dict_offset);
+                if (c.stats.present) write_statistics(t, 12, c.stats);
                 t.end_struct();
                 t.end_struct();
             }
@@ -246,6 +276,15 @@ int pf_writer_close(pf_writer* w) {
             t.end_struct();
         }
         t.binary(6, "parquet-floor_amd (GPU encoder; parquet-mr 1.12.2 ParquetWriter settings)");
+        if (w->any_stats) {   // column_orders: one ColumnOrder { 1: TYPE_ORDER {} } per leaf; readers trust min_value / max_value by it
+            t.list_header(7, T_STRUCT, w->fields.size());
+            for (size_t i = 0; i < w->fields.size(); i++) {
+                t.list_struct_begin();
+                t.begin_struct(1);
+                t.end_struct();
+                t.end_struct();
+            }
+        }
         t.stop();
         const uint32_t n = uint32_t(f.size());
         uint8_t tail[8];

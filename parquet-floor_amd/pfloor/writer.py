@@ -21,10 +21,18 @@ definition levels of an OPTIONAL column, and BOOLEAN chunks in the RLE encoding.
 levels are one bit-packed run per page and BOOLEAN is PLAIN. delta_fallback=True with
 hybrid_runs=True gives the encodings parquet-mr's PARQUET_2_0 writer gives.
 
+With statistics=True (PF_ENCODE_STATISTICS) every data page header and every ColumnMetaData carries a
+Statistics struct (null_count, min_value / max_value, and the legacy min / max where parquet-mr writes
+them), reduced on the GPU over the present values under ColumnOrder TYPE_ORDER, and the footer declares
+column_orders so that readers use them to skip row groups and pages. With page_checksums=True
+(PF_ENCODE_PAGE_CRC) every page header, dictionary pages included, carries PageHeader.crc, the CRC-32 of
+the stored page bytes, its pieces computed on the GPU; pf_scan_pages(verify_crc=1), parquet-mr and
+pyarrow verify it. With both off (the default) files are byte for byte what they were before.
+
 Differences that are allowed by the format and documented in DESIGN.md: the fallback is decided
 for the whole chunk (parquet-mr switches mid-chunk and also drops a dictionary that does not
 compress, isCompressionSatisfying), ids are written as one bit-packed run per page unless
-hybrid_runs is set, no page / column statistics are written.
+hybrid_runs is set, statistics and page checksums are opt-in, no column index / offset index is written.
 """
 import ctypes as C
 
@@ -35,6 +43,8 @@ from ._native import PfError, check, lib
 
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1, 2, 3, 4, 5, 6, 7
 ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK, ENCODE_HYBRID_RUNS = 1, 2, 4   # pf_encode_column.dictionary bits (PF_ENCODE_*)
+ENCODE_STATISTICS, ENCODE_PAGE_CRC = 8, 16
+STATS_NULL_COUNT, STATS_MIN_MAX = 1, 2   # pf_encoded_chunk.stats_flags (PF_STATS_*)
 _WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, FLOAT: 4, DOUBLE: 8}
 _DTYPE = {BOOLEAN: np.uint8, INT32: np.int32, INT64: np.int64, FLOAT: np.float32, DOUBLE: np.float64}
 _NAMES = {BOOLEAN: "BOOLEAN", INT32: "INT32", INT64: "INT64", INT96: "INT96", FLOAT: "FLOAT", DOUBLE: "DOUBLE",
@@ -53,7 +63,16 @@ class EncodedChunk(C.Structure):
                 ("num_values", C.c_int64), ("dictionary_page_offset", C.c_int64), ("data_page_offset", C.c_int64),
                 ("n_data_pages", C.c_int32), ("dict_entries", C.c_int32), ("data_encoding", C.c_int32),
                 ("fallback", C.c_int32), ("codec", C.c_int32), ("snappy_ms", C.c_float), ("encode_ms", C.c_float),
-                ("snappy_in", C.c_int64), ("snappy_out", C.c_int64)]
+                ("snappy_in", C.c_int64), ("snappy_out", C.c_int64),
+                ("stats_flags", C.c_int32), ("stat_min_len", C.c_int32), ("stat_max_len", C.c_int32),
+                ("null_count", C.c_int64), ("stat_min", C.c_void_p), ("stat_max", C.c_void_p)]
+
+    def statistics(self):
+        """(null_count or None, min bytes or None, max bytes or None) of the chunk."""
+        mm = bool(self.stats_flags & STATS_MIN_MAX)
+        return (self.null_count if self.stats_flags & STATS_NULL_COUNT else None,
+                C.string_at(self.stat_min, self.stat_min_len) if mm else None,
+                C.string_at(self.stat_max, self.stat_max_len) if mm else None)
 
 
 class WriteField(C.Structure):
@@ -186,10 +205,12 @@ class GpuColumnEncoder:
         self.dec = decoder
 
     def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1,
-               delta_fallback=False, hybrid_runs=False):
+               delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False):
         """delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
         dictionary-encoded (INT32, INT64, BINARY). hybrid_runs: PF_ENCODE_HYBRID_RUNS, ids, definition
-        levels and BOOLEAN values as parquet-mr's hybrid encoder writes them (RLE runs and bit-packed groups)."""
+        levels and BOOLEAN values as parquet-mr's hybrid encoder writes them (RLE runs and bit-packed groups).
+        statistics: PF_ENCODE_STATISTICS, page and chunk Statistics. page_checksums: PF_ENCODE_PAGE_CRC,
+        PageHeader.crc on every page."""
         c = EncodeColumn()
         c.physical_type = field.physical_type
         c.max_def = 1 if field.optional else 0
@@ -214,7 +235,8 @@ class GpuColumnEncoder:
             keep.append(v)
             c.validity = v.ctypes.data
         c.dictionary = ((ENCODE_DICTIONARY if dictionary else 0) | (ENCODE_DELTA_FALLBACK if delta_fallback else 0) |
-                        (ENCODE_HYBRID_RUNS if hybrid_runs else 0))
+                        (ENCODE_HYBRID_RUNS if hybrid_runs else 0) | (ENCODE_STATISTICS if statistics else 0) |
+                        (ENCODE_PAGE_CRC if page_checksums else 0))
         c.page_rows = page_rows
         c.dict_page_limit = dict_page_limit
         c.codec = codec
@@ -229,9 +251,11 @@ class ParquetWriter:
     block size; the bound here is in rows, the byte size of a row group is the caller's)."""
 
     def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=1,
-                 decoders=None, delta_fallback=False, hybrid_runs=False):
+                 decoders=None, delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False):
         """delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
         hybrid_runs: ids, definition levels and BOOLEAN values in parquet-mr's hybrid run shape (see above).
+        statistics: page and chunk Statistics and the footer's column_orders (see above).
+        page_checksums: PageHeader.crc on every page (see above).
         decoders: several contexts (GpuDecoder) to encode the columns of a row group in parallel
         (one host thread each); chunks are still appended in schema order."""
         from .decoder import GpuDecoder
@@ -245,6 +269,8 @@ class ParquetWriter:
         self.codec = codec
         self.delta_fallback = delta_fallback
         self.hybrid_runs = hybrid_runs
+        self.statistics = statistics
+        self.page_checksums = page_checksums
         self.buf = _RowBuffer(schema)
         self.last_chunks = []     # (dict_entries, data_encoding, fallback) of the last row group
         fields = (WriteField * len(schema.fields))()
@@ -310,10 +336,16 @@ class ParquetWriter:
                         i = order.pop(0)
                     f, d, validity = work[i]
                     out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
-                                     hybrid_runs=self.hybrid_runs)
+                                     hybrid_runs=self.hybrid_runs, statistics=self.statistics,
+                                     page_checksums=self.page_checksums)
                     keep = C.create_string_buffer(C.string_at(out.bytes, out.size), max(1, out.size))
                     cp = EncodedChunk.from_buffer_copy(out)
                     cp.bytes = C.cast(keep, C.c_void_p)
+                    if out.stats_flags & STATS_MIN_MAX:   # the context owns min / max too
+                        lo = C.create_string_buffer(C.string_at(out.stat_min, out.stat_min_len), max(1, out.stat_min_len))
+                        hi = C.create_string_buffer(C.string_at(out.stat_max, out.stat_max_len), max(1, out.stat_max_len))
+                        cp.stat_min, cp.stat_max = C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p)
+                        keep = (keep, lo, hi)
                     results[i] = (cp, keep)
             except Exception as e:   # reported after the join
                 errs.append(e)
@@ -338,7 +370,8 @@ class ParquetWriter:
 
     def _encode_add(self, f, data, validity, n, i):
         out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
-                              hybrid_runs=self.hybrid_runs)
+                              hybrid_runs=self.hybrid_runs, statistics=self.statistics,
+                              page_checksums=self.page_checksums)
         self._add(out, i)
         return out
 
