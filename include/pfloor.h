@@ -289,6 +289,10 @@ int pf_file_chunk_desc(pf_file* f, int row_group, int column, uint64_t chunk_off
                        pf_chunk_desc* desc);
 /* Read raw bytes of the file (host). */
 int pf_file_read(pf_file* f, uint64_t offset, uint64_t size, void* dst);
+/* The chunk's Bloom filter: *offset = ColumnMetaData.bloom_filter_offset (the file offset of its BloomFilterHeader), -1
+ * if it has none; *length = bloom_filter_length (header + bitset), -1 if the writer left it out (parquet-mr 1.12: read
+ * the header for numBytes). PF_ERR_IO if either points outside the file. */
+int pf_file_chunk_bloom(pf_file* f, int row_group, int column, int64_t* offset, int32_t* length);
 const char* pf_file_created_by(pf_file* f);
 
 /* ---- write path: the reference's ParquetWriter (ParquetWriter.java:61-165: SNAPPY,
@@ -296,7 +300,9 @@ const char* pf_file_created_by(pf_file* f);
  *      GPU: dictionary encode (entries in first-occurrence order, like parquet-mr's
  *      DictionaryValuesWriter), RLE/bit-packed hybrid ids, PLAIN values, Snappy compression of
  *      every page. Flat schemas of the types the reference writes (ParquetWriter.java:143-157):
- *      BOOLEAN, INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY (UTF8). ---- */
+ *      BOOLEAN, INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY (UTF8). Opt-in, also on the GPU: statistics, page CRCs
+ *      (PF_ENCODE_* bits below) and a split-block Bloom filter per chunk (pf_encode_column.bloom_bytes), which
+ *      pf_writer_close stores behind the last row group. ---- */
 /* pf_encode_column.dictionary is a bit set (0 and 1 keep the meaning they always had). */
 #define PF_ENCODE_DICTIONARY     1   /* dictionary-encode; the chunk falls back as a whole above
                                         dict_page_limit, on a hash collision, or for BOOLEAN */
@@ -339,6 +345,9 @@ typedef struct pf_encode_column {
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
     int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's) or PF_CODEC_UNCOMPRESSED */
+    int32_t  bloom_bytes;         /* split-block Bloom filter of the chunk's present values, filled on the GPU: its
+                                     size in bytes, a power of two in [32, 128 MiB] (else PF_ERR_INVALID_ARG);
+                                     0 = none, the bytes of every release before it. BOOLEAN: ignored, no filter */
 } pf_encode_column;
 
 typedef struct pf_encoded_chunk {
@@ -366,6 +375,15 @@ typedef struct pf_encoded_chunk {
     int64_t  null_count;
     const uint8_t* stat_min;      /* PLAIN bytes of the min / max (BYTE_ARRAY: no length prefix); owned by the ctx, */
     const uint8_t* stat_max;      /* valid until its next pf_encode_chunk, like bytes */
+    /* Split-block Bloom filter (pf_encode_column.bloom_bytes; bloom_len 0: none): XXH64, seed 0, of the PLAIN bytes of
+     * every present value (BYTE_ARRAY: without the length prefix; FLOAT / DOUBLE: the bits, so NaN payloads count and
+     * -0.0 and +0.0 are two values) sets one bit in each of the eight uint32 words of the 32-byte block
+     * ((hash >> 32) * blocks) >> 32. It does not depend on how the chunk was encoded. pf_writer_add_chunk copies it;
+     * pf_writer_close stores it with its BloomFilterHeader behind the last row group. */
+    const uint8_t* bloom;         /* the bitset alone, words little-endian; owned by the ctx, valid until its next
+                                     pf_encode_chunk, like bytes */
+    int32_t  bloom_len;
+    float    bloom_ms;            /* the filter's zeroing and k_enc_bloom (HIP events; 0 when timing is off); not in encode_ms */
 } pf_encoded_chunk;
 
 /* Encode one column chunk on the context's GPU. Inputs are host memory (copied) unless
@@ -385,12 +403,23 @@ typedef struct pf_write_field {
     int32_t utf8;                 /* BYTE_ARRAY: STRING logical type (the only BINARY the reference writes) */
 } pf_write_field;
 int pf_writer_open(const char* path, const pf_write_field* fields, int n_fields, pf_writer** out);
-/* Append the chunk of field `field` (fields in schema order) to the current row group. */
+/* Append the chunk of field `field` (fields in schema order) to the current row group. A Bloom filter
+ * (bloom_len > 0: a power of two >= 32, bloom not null, else PF_ERR_INVALID_ARG) is copied and kept until close. */
 int pf_writer_add_chunk(pf_writer* w, int field, const pf_encoded_chunk* chunk);
 int pf_writer_end_row_group(pf_writer* w, int64_t num_rows);
-int pf_writer_close(pf_writer* w);   /* footer; frees w (also on error) */
+/* Bloom filters (BloomFilterHeader {1 numBytes, 2 BLOCK, 3 XXHASH, 4 UNCOMPRESSED} + bitset each, in row-group then
+ * column order, behind the last row group, where parquet-mr 1.12 and pyarrow put them; ColumnMetaData
+ * bloom_filter_offset 14 / bloom_filter_length 15), then the footer; frees w (also on error). */
+int pf_writer_close(pf_writer* w);
 const char* pf_writer_last_error(void);
 const char* pf_file_last_error(void);            /* thread-local message of the last pf_file_* error */
+
+/* ---- probing a Bloom filter on the host (no context, no GPU): the hash and the block arithmetic are the text the
+ *      kernel compiles (csrc/pf_xxh64.h). hash = pf_xxh64(PLAIN bytes of the value, n, 0). ---- */
+uint64_t pf_xxh64(const void* p, size_t n, uint64_t seed);
+/* 1: the value may be in the chunk; 0: it is not; PF_ERR_INVALID_ARG: n_bytes is no power of two in [32, 128 MiB].
+ * bitset: the n_bytes behind the BloomFilterHeader. */
+int pf_bloom_check(const uint8_t* bitset, size_t n_bytes, uint64_t hash);
 
 #ifdef __cplusplus
 }

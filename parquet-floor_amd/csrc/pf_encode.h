@@ -156,6 +156,11 @@ struct CrcOut {
 };
 void launch_enc_crc(const CrcPiece* d_pieces, int n_pieces, CrcOut* d_out, hipStream_t st);
 
+// ---- split-block Bloom filter (pf_enc_bloom.hip; pf_encode_column.bloom_bytes) ----
+// `filter`: bloom_bytes zeroed bytes, a power of two >= 32. first_only: hash only the dense values with mark set
+// (a dictionary-encoded chunk's first occurrences).
+void enc_bloom(const EncArgs& a, uint32_t m, uint32_t* filter, uint32_t bloom_bytes, bool first_only, hipStream_t st);
+
 hipError_t enc_scan_temp(size_t n, size_t& bytes);
 hipError_t enc_dense(const EncArgs& a, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t enc_plain_sizes(const EncArgs& a, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);

@@ -3,6 +3,8 @@
 // (ParquetReader.java:126-128) and build pf_chunk_desc for a row group's chunks
 // (readNextRowGroup, ParquetReader.java:183). No GPU calls.
 #include <cerrno>
+#include <climits>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -100,6 +102,23 @@ int pf_file_chunk_range(pf_file* f, int rg, int col, uint64_t* start, uint64_t* 
         return ferr(PF_ERR_IO, "column chunk outside the file");
     *start = uint64_t(s);
     *size = uint64_t(m.total_compressed);
+    return PF_OK;
+}
+
+int pf_file_chunk_bloom(pf_file* f, int rg, int col, int64_t* offset, int32_t* length) {
+    if (!f || !offset || !length || rg < 0 || rg >= int(f->meta.row_groups.size()) || col < 0 ||
+        col >= int(f->meta.leaves.size()))
+        return ferr(PF_ERR_INVALID_ARG, "bad index");
+    const pf::ChunkMeta& m = f->meta.row_groups[rg].columns[col];
+    *offset = -1;
+    *length = -1;
+    if (m.bloom_offset == -1 && m.bloom_length == -1) return PF_OK;
+    const bool has_len = m.bloom_length != -1;
+    if (m.bloom_offset < 4 || uint64_t(m.bloom_offset) >= f->size ||
+        (has_len && (m.bloom_length < 0 || m.bloom_length > INT32_MAX || uint64_t(m.bloom_offset) + uint64_t(m.bloom_length) > f->size)))
+        return ferr(PF_ERR_IO, "Bloom filter outside the file");
+    *offset = m.bloom_offset;
+    if (has_len) *length = int32_t(m.bloom_length);
     return PF_OK;
 }
 

@@ -19,6 +19,7 @@ struct ChunkMeta {
     int64_t num_values = 0, total_uncompressed = 0, total_compressed = 0;
     int64_t data_page_offset = 0, dictionary_page_offset = 0;
     bool has_dict = false;
+    int64_t bloom_offset = -1, bloom_length = -1;   // ColumnMetaData 14 / 15 (-1: absent)
     // ColumnChunkMetaData.getStartingPos(): the dictionary page offset when it precedes
     // the first data page, else the data page offset.
     int64_t start() const {

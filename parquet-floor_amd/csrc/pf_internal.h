@@ -51,6 +51,7 @@ struct PfOpts {
     int64_t nest_seg = 0;     // PF_NEST_SEG=n: nested segment length, forced (0: default, not forced)
     bool nest_seg_set = false;
     bool dbp_par = true;      // PF_DBP_PAR=0: every DELTA_BINARY_PACKED page on k_delta
+    bool bloom_first = true;  // PF_BLOOM_FIRST=0: a dictionary-encoded chunk's Bloom filter hashes every value, not the first occurrences
     int fix_shift = 1;        // PF_FIX_BLK=4096|8192|16384: fixed-width flat blocks (log2 of the multiple of 4096)
 };
 

@@ -160,6 +160,8 @@ ChunkMeta read_column_chunk(ThriftReader& r) {
                 case 7: m.total_compressed = r.integer(t2); break;
                 case 9: m.data_page_offset = r.integer(t2); break;
                 case 11: m.dictionary_page_offset = r.integer(t2); m.has_dict = true; break;
+                case 14: m.bloom_offset = r.integer(t2); break;
+                case 15: m.bloom_length = r.integer(t2); break;
                 default: r.skip(t2);
                 }
             }

@@ -25,6 +25,7 @@
 #include "pf_launch.h"
 #include "pf_plan.h"
 #include "pf_snappy_par.h"
+#include "pf_xxh64.h"
 #include "pfloor.h"
 
 using namespace pf;
@@ -165,6 +166,7 @@ struct pf_ctx {
     // wait for it, not for the stream, so a peer's decode queued behind the copies keeps running
     hipEvent_t ev_copy = nullptr;          // after this context's last async copy (on whichever stream)
     hipEvent_t ev_dl = nullptr;            // the decode a download on the copy stream follows
+    hipEvent_t ev_bloom[2] = {};           // pf_encode_chunk: around the Bloom filter's fill (pf_encoded_chunk.bloom_ms)
     bool timing = true;                    // per-stage events (pf_last_timing); pf_ctx_set_timing
     std::string err;
     DevBuf d_in, d_scratch, d_out, d_bits, d_chars, d_meta, d_tokmap;
@@ -173,6 +175,7 @@ struct pf_ctx {
     std::vector<uint8_t> h_enc;            // the last encoded chunk (headers + bodies)
     std::vector<uint8_t> h_enc_stat;       // its chunk statistics (min ‖ max)
     HostBuf h_enc_st;                      // pf_encode_chunk: statistics results D2H
+    HostBuf h_enc_bloom;                   // pf_encode_chunk: the Bloom filter's bitset D2H (pf_encoded_chunk.bloom)
     HostBuf h_meta, h_res;
     HostBuf h_enc_slots;                   // pf_encode_chunk / pf_snappy_compress: compressed slots D2H
     // last batch
@@ -513,6 +516,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     if (n < 0 || n > 0x7ffffff0 || (col->max_def != 0 && col->max_def != 1)) return fail(ctx, PF_ERR_INVALID_ARG, "encode: bad shape");
     if (col->codec != PF_CODEC_SNAPPY && col->codec != PF_CODEC_UNCOMPRESSED)
         return fail(ctx, PF_ERR_UNSUPPORTED_CODEC, "encode: codec must be SNAPPY or UNCOMPRESSED");
+    if (col->bloom_bytes != 0 && (col->bloom_bytes < 0 || !bloom_size_ok(uint64_t(col->bloom_bytes))))
+        return fail(ctx, PF_ERR_INVALID_ARG, "encode: bloom_bytes must be a power of two in [32, 128 MiB]");
+    const size_t bloom = pt == PF_BOOLEAN ? 0 : size_t(col->bloom_bytes);   // BOOLEAN: no filter (parquet-mr builds none)
     const bool str = pt == PF_BYTE_ARRAY;
     if (n > 0 && (str ? (!col->offsets || (!col->chars && col->chars_len > 0) || col->chars_len < 0 || col->chars_len > 0x7fffffff)
                       : !col->values))
@@ -630,6 +636,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     size_t temp_bytes = 0;
     HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
     const size_t o_temp = take(a_sz, temp_bytes);
+    const size_t o_bloom = bloom ? take(a_sz, bloom) : 0;
     HIPCHK(ctx, ctx->d_enc.ensure(a_sz));
     uint8_t* A = static_cast<uint8_t*>(ctx->d_enc.p);
     EncArgs ea{};
@@ -785,6 +792,19 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         if (str) HIPCHK(ctx, hipMemcpyAsync(h + sizeof(StatPart) * n_se, A + o_sbytes, size_t(ST_LIMIT) * n_se, hipMemcpyDeviceToHost, st));
         return PF_OK;
     };
+    // Bloom filter (bloom_bytes): zeroed and filled on the stream behind the page kernels, outside encode_ms (events of
+    // its own); the bitset comes back in pinned memory with the copy and synchronisation the bodies wait for anyway.
+    auto bloom_launch = [&]() -> int {
+        if (!bloom) return PF_OK;
+        HIPCHK(ctx, ctx->h_enc_bloom.ensure(bloom));
+        EVREC(ctx, ctx->ev_bloom[0], st);
+        HIPCHK(ctx, hipMemsetAsync(A + o_bloom, 0, bloom, st));
+        enc_bloom(ea, m, reinterpret_cast<uint32_t*>(A + o_bloom), uint32_t(bloom), dict && ctx->opts.bloom_first, st);
+        HIPCHK(ctx, hipGetLastError());
+        EVREC(ctx, ctx->ev_bloom[1], st);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_enc_bloom.p, A + o_bloom, bloom, hipMemcpyDeviceToHost, st));
+        return PF_OK;
+    };
     if (hyb && delta) {
         const int rc = hybrid_sizes();
         if (rc) return rc;
@@ -834,6 +854,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         if (const int rc = stats_launch()) return rc;
         EVREC(ctx, ctx->ev[5], st);
         if (const int rc = stats_fetch()) return rc;
+        if (const int rc = bloom_launch()) return rc;
     }
     uint8_t* SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
     if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size (hybrid runs: after their size pass)
@@ -890,6 +911,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         if (const int rc = stats_launch()) return rc;
         EVREC(ctx, ctx->ev[5], st);
         if (const int rc = stats_fetch()) return rc;
+        if (const int rc = bloom_launch()) return rc;
     }
     std::vector<std::vector<uint8_t>> bodies;
     std::vector<uint8_t> hlv(lv_total);   // hybrid runs: the pages' levels
@@ -1095,6 +1117,10 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     }
     out->snappy_ms = snap_ms;
     out->encode_ms = enc_ms;
+    out->bloom = bloom ? static_cast<const uint8_t*>(ctx->h_enc_bloom.p) : nullptr;
+    out->bloom_len = int32_t(bloom);
+    out->bloom_ms = 0.f;
+    if (bloom && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&out->bloom_ms, ctx->ev_bloom[0], ctx->ev_bloom[1]));
     out->snappy_in = 0;
     out->snappy_out = 0;
     if (col->codec == PF_CODEC_SNAPPY)
@@ -1151,6 +1177,7 @@ void opts_from_env(pf::PfOpts& o) {
         o.nest_seg_set = true;
     }
     o.dbp_par = on("PF_DBP_PAR", o.dbp_par);
+    o.bloom_first = on("PF_BLOOM_FIRST", o.bloom_first);
     const int fb = num("PF_FIX_BLK", 8192);
     o.fix_shift = fb >= 16384 ? 2 : (fb >= 8192 ? 1 : 0);
 }
@@ -1174,6 +1201,7 @@ int ctx_init(pf_ctx* ctx, pf_ctx* peer) {
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_copy, hipEventDisableTiming));
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_dl, hipEventDisableTiming));
     for (auto& e : ctx->ev) HIPCHK(nullptr, hipEventCreate(&e));
+    for (auto& e : ctx->ev_bloom) HIPCHK(nullptr, hipEventCreate(&e));
     return PF_OK;
 }
 
@@ -1227,7 +1255,9 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_res.release();
     ctx->h_enc_slots.release();
     ctx->h_enc_st.release();
+    ctx->h_enc_bloom.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->ev_bloom) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
     if (ctx->ev_dl) (void)hipEventDestroy(ctx->ev_dl);

@@ -104,6 +104,9 @@ struct ChunkRec {
     int64_t file_offset = 0, size = 0, uncompressed = 0, num_values = 0, dict_offset = -1, data_offset = 0;
     int32_t data_encoding = 0, codec = 0;
     StatsOut stats;
+    std::vector<uint8_t> bloom;   // the Bloom filter's bitset, kept until close (empty: none)
+    int64_t bloom_offset = -1;    // file offset of its BloomFilterHeader
+    int32_t bloom_length = 0;     // header + bitset
 };
 struct RowGroupRec {
     int64_t num_rows = 0;
@@ -182,6 +185,11 @@ int pf_writer_add_chunk(pf_writer* w, int field, const pf_encoded_chunk* c) {
         r.stats.present = true;
         r.stats.null_count = c->null_count;
     }
+    if (c->bloom_len != 0) {
+        if (c->bloom_len < 32 || (c->bloom_len & (c->bloom_len - 1)) != 0 || !c->bloom)
+            return werr(PF_ERR_INVALID_ARG, "chunk Bloom filter: bloom_len must be a power of two >= 32 and bloom not null");
+        r.bloom.assign(c->bloom, c->bloom + c->bloom_len);
+    }
     int rc = put(w, c->bytes, size_t(c->size));
     if (rc) return rc;
     if (r.stats.present) w->any_stats = true;
@@ -200,11 +208,32 @@ int pf_writer_end_row_group(pf_writer* w, int64_t num_rows) {
     return PF_OK;
 }
 
+// Bloom filters, behind the last row group in row-group then column order (parquet-mr 1.12 ParquetFileWriter.end,
+// pyarrow): BloomFilterHeader { 1 numBytes, 2 algorithm { 1 BLOCK {} }, 3 hash { 1 XXHASH {} }, 4 compression
+// { 1 UNCOMPRESSED {} } }, then the bitset.
 // FileMetaData: 1 version, 2 schema, 3 num_rows, 4 row_groups, 6 created_by, 7 column_orders (only with statistics).
 int pf_writer_close(pf_writer* w) {
     if (!w) return werr(PF_ERR_INVALID_ARG, "null writer");
     int rc = PF_OK;
     if (!w->cur.chunks.empty()) rc = werr(PF_ERR_STATE, "unfinished row group");
+    for (RowGroupRec& g : w->groups)
+        for (ChunkRec& c : g.chunks) {
+            if (c.bloom.empty() || rc != PF_OK || w->failed) continue;
+            std::vector<uint8_t> h;
+            ThriftWriter t(h);
+            t.i32(1, int64_t(c.bloom.size()));
+            for (int id = 2; id <= 4; id++) {
+                t.begin_struct(id);
+                t.begin_struct(1);
+                t.end_struct();
+                t.end_struct();
+            }
+            t.stop();
+            c.bloom_offset = w->pos;
+            c.bloom_length = int32_t(h.size() + c.bloom.size());
+            rc = put(w, h.data(), h.size());
+            if (!rc) rc = put(w, c.bloom.data(), c.bloom.size());
+        }
     if (rc == PF_OK && !w->failed) {
         std::vector<uint8_t> f;
         ThriftWriter t(f);
@@ -266,6 +295,10 @@ int pf_writer_close(pf_writer* w) {
                 t.i64(9, c.data_offset);
                 if (c.dict_offset >= 0) t.i64(11, c.dict_offset);
                 if (c.stats.present) write_statistics(t, 12, c.stats);
+                if (c.bloom_offset >= 0) {   // bloom_filter_offset, bloom_filter_length (parquet-mr 1.12.2 skips the latter)
+                    t.i64(14, c.bloom_offset);
+                    t.i32(15, c.bloom_length);
+                }
                 t.end_struct();
                 t.end_struct();
             }

@@ -151,6 +151,9 @@ def _load(path):
         "pf_file_chunk_range": ([vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
         "pf_file_chunk_desc": ([vp, i32, i32, C.c_uint64, C.POINTER(ChunkDesc)], C.c_int),
         "pf_file_read": ([vp, C.c_uint64, C.c_uint64, vp], C.c_int),
+        "pf_file_chunk_bloom": ([vp, i32, i32, i64p, C.POINTER(C.c_int32)], C.c_int),
+        "pf_xxh64": ([vp, sz, C.c_uint64], C.c_uint64),
+        "pf_bloom_check": ([vp, sz, C.c_uint64], C.c_int),
         "pf_file_created_by": ([vp], C.c_char_p),
         "pf_file_last_error": ([], C.c_char_p),
         "pf_encode_chunk": ([vp, vp, i32, vp], C.c_int),

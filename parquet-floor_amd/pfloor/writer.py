@@ -29,12 +29,21 @@ column_orders so that readers use them to skip row groups and pages. With page_c
 the stored page bytes, its pieces computed on the GPU; pf_scan_pages(verify_crc=1), parquet-mr and
 pyarrow verify it. With both off (the default) files are byte for byte what they were before.
 
+With bloom_filters={name: ...} the named columns get a split-block Bloom filter (parquet-mr's
+parquet.bloom.filter.enabled#name): XXH64 of the PLAIN bytes of every present value of a chunk, hashed and
+inserted on the GPU (pf_encode_column.bloom_bytes), stored with its BloomFilterHeader behind the last row group
+and located by ColumnMetaData.bloom_filter_offset / bloom_filter_length, where parquet-mr, Arrow C++, Impala,
+Trino and DuckDB look for it to answer = and IN predicates. The size comes from an expected distinct count and
+a false-positive probability (bloom_optimal_bytes, Arrow's and parquet-mr's formula), capped at bloom_max_bytes.
+The filter does not depend on how the chunk is encoded. BOOLEAN columns get none.
+
 Differences that are allowed by the format and documented in DESIGN.md: the fallback is decided
 for the whole chunk (parquet-mr switches mid-chunk and also drops a dictionary that does not
 compress, isCompressionSatisfying), ids are written as one bit-packed run per page unless
-hybrid_runs is set, statistics and page checksums are opt-in, no column index / offset index is written.
+hybrid_runs is set, statistics, page checksums and Bloom filters are opt-in, no column index / offset index is written.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -45,6 +54,7 @@ BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1
 ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK, ENCODE_HYBRID_RUNS = 1, 2, 4   # pf_encode_column.dictionary bits (PF_ENCODE_*)
 ENCODE_STATISTICS, ENCODE_PAGE_CRC = 8, 16
 STATS_NULL_COUNT, STATS_MIN_MAX = 1, 2   # pf_encoded_chunk.stats_flags (PF_STATS_*)
+BLOOM_MIN_BYTES, BLOOM_MAX_BYTES = 32, 128 << 20   # pf_encode_column.bloom_bytes: a power of two between them
 _WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, FLOAT: 4, DOUBLE: 8}
 _DTYPE = {BOOLEAN: np.uint8, INT32: np.int32, INT64: np.int64, FLOAT: np.float32, DOUBLE: np.float64}
 _NAMES = {BOOLEAN: "BOOLEAN", INT32: "INT32", INT64: "INT64", INT96: "INT96", FLOAT: "FLOAT", DOUBLE: "DOUBLE",
@@ -55,7 +65,7 @@ class EncodeColumn(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("max_def", C.c_int32), ("num_rows", C.c_int64),
                 ("values", C.c_void_p), ("validity", C.c_void_p), ("offsets", C.c_void_p), ("chars", C.c_void_p),
                 ("chars_len", C.c_int64), ("dictionary", C.c_int32), ("page_rows", C.c_int32),
-                ("dict_page_limit", C.c_int32), ("codec", C.c_int32)]
+                ("dict_page_limit", C.c_int32), ("codec", C.c_int32), ("bloom_bytes", C.c_int32)]
 
 
 class EncodedChunk(C.Structure):
@@ -65,7 +75,8 @@ class EncodedChunk(C.Structure):
                 ("fallback", C.c_int32), ("codec", C.c_int32), ("snappy_ms", C.c_float), ("encode_ms", C.c_float),
                 ("snappy_in", C.c_int64), ("snappy_out", C.c_int64),
                 ("stats_flags", C.c_int32), ("stat_min_len", C.c_int32), ("stat_max_len", C.c_int32),
-                ("null_count", C.c_int64), ("stat_min", C.c_void_p), ("stat_max", C.c_void_p)]
+                ("null_count", C.c_int64), ("stat_min", C.c_void_p), ("stat_max", C.c_void_p),
+                ("bloom", C.c_void_p), ("bloom_len", C.c_int32), ("bloom_ms", C.c_float)]
 
     def statistics(self):
         """(null_count or None, min bytes or None, max bytes or None) of the chunk."""
@@ -73,6 +84,32 @@ class EncodedChunk(C.Structure):
         return (self.null_count if self.stats_flags & STATS_NULL_COUNT else None,
                 C.string_at(self.stat_min, self.stat_min_len) if mm else None,
                 C.string_at(self.stat_max, self.stat_max_len) if mm else None)
+
+    def bloom_filter(self):
+        """The chunk's split-block Bloom filter (the bitset alone, bloom_len bytes), or None."""
+        return C.string_at(self.bloom, self.bloom_len) if self.bloom_len > 0 else None
+
+
+def _bloom_cap(max_bytes):
+    """max_bytes as a filter size: the largest power of two not above it, within the format's 32 bytes .. 128 MiB."""
+    if max_bytes < BLOOM_MIN_BYTES:
+        raise ValueError("bloom max_bytes must be >= 32")
+    return min(1 << (int(max_bytes).bit_length() - 1), BLOOM_MAX_BYTES)
+
+
+def bloom_optimal_bytes(ndv, fpp=0.01, max_bytes=1 << 20):
+    """Bytes of a split-block Bloom filter for `ndv` distinct values at false-positive probability `fpp`:
+    bits = -8 ndv / ln(1 - fpp^(1/8)) (eight bits per value and block: parquet-mr BlockSplitBloomFilter.optimalNumOfBits,
+    Arrow BlockSplitBloomFilter::OptimalNumOfBits), rounded up to a power of two, at least 32 bytes and at most
+    max_bytes (parquet.bloom.filter.max.bytes; rounded down to a power of two)."""
+    if not 0.0 < fpp < 1.0 or ndv < 0:
+        raise ValueError("fpp must be in (0, 1) and ndv >= 0")
+    cap = _bloom_cap(max_bytes)
+    bits = int(-8.0 * ndv / math.log(1.0 - fpp ** (1.0 / 8.0)))
+    bits = max(bits, BLOOM_MIN_BYTES * 8)
+    if bits & (bits - 1):
+        bits = 1 << bits.bit_length()
+    return min(bits >> 3, cap)
 
 
 class WriteField(C.Structure):
@@ -205,8 +242,9 @@ class GpuColumnEncoder:
         self.dec = decoder
 
     def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1,
-               delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False):
-        """delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
+               delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False, bloom_bytes=0):
+        """bloom_bytes: the chunk's split-block Bloom filter, a power of two in [32, 128 MiB] (0: none;
+        EncodedChunk.bloom_filter()). delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
         dictionary-encoded (INT32, INT64, BINARY). hybrid_runs: PF_ENCODE_HYBRID_RUNS, ids, definition
         levels and BOOLEAN values as parquet-mr's hybrid encoder writes them (RLE runs and bit-packed groups).
         statistics: PF_ENCODE_STATISTICS, page and chunk Statistics. page_checksums: PF_ENCODE_PAGE_CRC,
@@ -240,6 +278,7 @@ class GpuColumnEncoder:
         c.page_rows = page_rows
         c.dict_page_limit = dict_page_limit
         c.codec = codec
+        c.bloom_bytes = bloom_bytes
         out = EncodedChunk()
         check(lib().pf_encode_chunk(self.dec.h, C.byref(c), 0, C.byref(out)), self.dec.h, "pf_encode_chunk")
         return out
@@ -251,8 +290,12 @@ class ParquetWriter:
     block size; the bound here is in rows, the byte size of a row group is the caller's)."""
 
     def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=1,
-                 decoders=None, delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False):
-        """delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
+                 decoders=None, delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False,
+                 bloom_filters=None, bloom_fpp=0.01, bloom_max_bytes=1 << 20):
+        """bloom_filters: {field name: expected distinct count | True (bloom_max_bytes) | {"bytes": n}}, the columns
+        that get a Bloom filter, sized by bloom_optimal_bytes(ndv, bloom_fpp, bloom_max_bytes) (see above); an unknown
+        name is a ValueError, a BOOLEAN field gets none.
+        delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
         hybrid_runs: ids, definition levels and BOOLEAN values in parquet-mr's hybrid run shape (see above).
         statistics: page and chunk Statistics and the footer's column_orders (see above).
         page_checksums: PageHeader.crc on every page (see above).
@@ -260,6 +303,7 @@ class ParquetWriter:
         (one host thread each); chunks are still appended in schema order."""
         from .decoder import GpuDecoder
         self.schema, self.dehydrator = schema, dehydrator
+        self.bloom_bytes = self._bloom_sizes(schema, bloom_filters, bloom_fpp, bloom_max_bytes)
         self.row_group_rows = row_group_rows
         self._own = decoder is None and not decoders
         self.dec = decoder or (decoders[0] if decoders else GpuDecoder(device))
@@ -283,6 +327,25 @@ class ParquetWriter:
             if self._own:
                 self.dec.close()
             raise PfError(rc, "pf_writer_open: " + (lib().pf_writer_last_error() or b"").decode(errors="replace"))
+
+    @staticmethod
+    def _bloom_sizes(schema, spec, fpp, max_bytes):
+        """bloom_filters -> filter bytes per field of the schema (0: none)."""
+        sizes = [0] * len(schema.fields)
+        for name, how in (spec or {}).items():
+            if name not in schema._index:
+                raise ValueError(f"bloom_filters: no field {name!r} in {schema.name}")
+            if how is True:     # no distinct count: the cap, as parquet-mr 1.12 sizes it
+                nbytes = _bloom_cap(max_bytes)
+            elif isinstance(how, dict):
+                nbytes = int(how["bytes"])
+                if not (BLOOM_MIN_BYTES <= nbytes <= BLOOM_MAX_BYTES) or nbytes & (nbytes - 1):
+                    raise ValueError(f"bloom_filters[{name!r}]: bytes must be a power of two in [32, 128 MiB]")
+            else:
+                nbytes = bloom_optimal_bytes(int(how), fpp, max_bytes)
+            if schema.fields[schema._index[name]].physical_type != BOOLEAN:   # parquet-mr builds none for BOOLEAN
+                sizes[schema._index[name]] = nbytes
+        return sizes
 
     @staticmethod
     def writeFile(schema, out, dehydrator, **kw):
@@ -337,10 +400,14 @@ class ParquetWriter:
                     f, d, validity = work[i]
                     out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
                                      hybrid_runs=self.hybrid_runs, statistics=self.statistics,
-                                     page_checksums=self.page_checksums)
+                                     page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i])
                     keep = C.create_string_buffer(C.string_at(out.bytes, out.size), max(1, out.size))
                     cp = EncodedChunk.from_buffer_copy(out)
                     cp.bytes = C.cast(keep, C.c_void_p)
+                    if out.bloom_len > 0:   # the context owns the filter too
+                        bf = C.create_string_buffer(out.bloom_filter(), out.bloom_len)
+                        cp.bloom = C.cast(bf, C.c_void_p)
+                        keep = (keep, bf)
                     if out.stats_flags & STATS_MIN_MAX:   # the context owns min / max too
                         lo = C.create_string_buffer(C.string_at(out.stat_min, out.stat_min_len), max(1, out.stat_min_len))
                         hi = C.create_string_buffer(C.string_at(out.stat_max, out.stat_max_len), max(1, out.stat_max_len))
@@ -371,7 +438,7 @@ class ParquetWriter:
     def _encode_add(self, f, data, validity, n, i):
         out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
                               hybrid_runs=self.hybrid_runs, statistics=self.statistics,
-                              page_checksums=self.page_checksums)
+                              page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i])
         self._add(out, i)
         return out
 
@@ -410,5 +477,5 @@ class ParquetWriter:
         self.close()
 
 
-__all__ = ["ParquetWriter", "MessageType", "Field", "Dehydrator", "ValueWriter", "required", "optional",
+__all__ = ["ParquetWriter", "bloom_optimal_bytes", "MessageType", "Field", "Dehydrator", "ValueWriter", "required", "optional",
            "BOOLEAN", "INT32", "INT64", "FLOAT", "DOUBLE", "BINARY", "_native"]
