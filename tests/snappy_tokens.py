@@ -8,6 +8,10 @@ output). Neither the oracle nor a library is called: test_snappy_tokens.py check
 oracle and pyarrow's Google Snappy read every stream the same way, and test_gpu_snappy_tokens.py then
 asks the kernels.
 
+parse() is the assembler's inverse (stream -> token list) and compressor_errors() holds a parsed stream to the
+grammar of k_snappy_compress: test_gpu_snappy_compress.py and test_gpu_write_bytes.py read the compressor's own
+choices with them.
+
 valid_corpus() / invalid_corpus() return the case tables, grouped by the letters of the comments below.
 A valid case is (name, stream, expected, fb, tags) with fb the pf_snappy_last_fallback code it must take
 and tags the tag byte values of its tokens; an invalid one is (name, stream, declared length). The decoder constants a case guards are named next to it (they are today's values: a retune moves the
@@ -49,6 +53,7 @@ class Stream:
         self.pre = pre
         self.pad = pad
         self.tags = set()      # tag bytes emitted as valid tokens
+        self.tokens = []       # (kind, offset, length, position in the body, output position): what parse() must find
         self.valid = True
 
     # ---- positions
@@ -83,6 +88,7 @@ class Stream:
             self.body += n.to_bytes(nb, "little")
         self.tags.add(tag)
         self.body += data
+        self.tokens.append((0, 0, len(data), len(self.body) - len(data) - 1 - nb, len(self.out)))
         self.out += data
         return self
 
@@ -102,6 +108,7 @@ class Stream:
             enc = bytes([tag]) + offset.to_bytes(4, "little")
         assert offset <= len(self.out), "copy reaches before the output start"
         self.tags.add(tag)
+        self.tokens.append((kind, offset, length, len(self.body), len(self.out)))
         self.body += enc
         a = len(self.out) - offset
         if offset >= length:
@@ -197,11 +204,162 @@ def mixed_block_tokens(s, nbytes):
     return s
 
 
+# ============================================================================ the token parser
+# The inverse of Stream, by the plain definition of the format: what a compressor emitted, token by token
+# (test_gpu_snappy_compress.py reads k_snappy_compress's choices off it). test_snappy_tokens.py checks that
+# it finds in every stream of valid_corpus() the tokens the assembler put there.
+
+LITERAL, COPY1, COPY2, COPY4 = 0, 1, 2, 3     # token kinds = the tag's low two bits (Stream.copy's `kind`)
+
+
+def parse(stream):
+    """stream -> (declared length, [(kind, offset, length, in_pos, out_pos)]).
+
+    kind: LITERAL / COPY1 / COPY2 / COPY4; offset: 0 for a literal; length: output bytes of the token;
+    in_pos: position of its tag byte in `stream`; out_pos: output position it starts at. A stream that is
+    not valid Snappy (truncated token, offset 0 or before the output start, output != declared length)
+    raises ValueError."""
+    stream = bytes(stream)
+    i, declared, sh = 0, 0, 0
+    while True:
+        if i >= len(stream) or sh > 28:
+            raise ValueError("bad length preamble")
+        c = stream[i]
+        i += 1
+        declared |= (c & 0x7F) << sh
+        sh += 7
+        if not c & 0x80:
+            break
+    tokens, op, n = [], 0, len(stream)
+    while i < n:
+        tag, at = stream[i], i
+        kind, hi = tag & 3, tag >> 2
+        if kind == LITERAL:
+            nb = hi - 59 if hi >= 60 else 0
+            if i + 1 + nb > n:
+                raise ValueError(f"literal length field cut off at input byte {at}")
+            ln = (int.from_bytes(stream[i + 1:i + 1 + nb], "little") if nb else hi) + 1
+            i += 1 + nb + ln
+            off = 0
+        else:
+            opnd = (1, 2, 4)[kind - 1]
+            if i + 1 + opnd > n:
+                raise ValueError(f"copy operand cut off at input byte {at}")
+            if kind == COPY1:
+                ln, off = 4 + (hi & 7), ((tag >> 5) << 8) | stream[i + 1]
+            else:
+                ln, off = hi + 1, int.from_bytes(stream[i + 1:i + 1 + opnd], "little")
+            i += 1 + opnd
+            if off == 0 or off > op:
+                raise ValueError(f"copy at input byte {at}: offset {off} with {op} bytes of output")
+        if i > n:
+            raise ValueError(f"literal data cut off (token at input byte {at})")
+        tokens.append((kind, off, ln, at, op))
+        op += ln
+    if op != declared:
+        raise ValueError(f"tokens give {op} bytes, preamble declares {declared}")
+    return declared, tokens
+
+
+def token_sizes(stream, tokens):
+    """Input bytes of every token (tag, operand / length field, literal data)."""
+    ends = [t[3] for t in tokens[1:]] + [len(stream)]
+    return [e - t[3] for t, e in zip(tokens, ends)]
+
+
+def expand(stream, tokens):
+    """The output of a parsed stream: literals append their data, copies append byte by byte."""
+    out = bytearray()
+    for (kind, off, ln, at, op), size in zip(tokens, token_sizes(stream, tokens)):
+        assert op == len(out)
+        if kind == LITERAL:
+            out += stream[at + size - ln:at + size]
+        elif off >= ln:
+            out += out[op - off:op - off + ln]
+        else:
+            for k in range(ln):
+                out.append(out[op - off + k])
+    return bytes(out)
+
+
+# ============================================================================ the compressor's grammar
+# What k_snappy_compress (pf_encode.hip) promises about its own streams, read off the parsed tokens. One
+# wave compresses one job of JOB input bytes on its own, and a page's stream is the preamble followed by
+# its jobs' outputs, so the tokens of job j are those whose output starts in [j * JOB, (j + 1) * JOB).
+
+JOB = 8192          # SC_BLOCK (pf_encode.h)
+
+
+def job_bound(n):
+    """Most bytes a job of n input bytes may take: n + n // 65 + 3.
+
+    From the format: a literal of l bytes costs l + h with h = 1 (l <= 60), 2 (l <= 256) or 3; a copy of
+    >= 4 bytes costs <= 3, so it saves >= 1. The compressor emits a literal only in front of a copy or as
+    the job's last token, so every literal but the last pairs with the copy behind it, and the pair costs
+    at most h - 1 over its bytes: 0 up to 60 literal bytes, 1 from 61 (the pair then covers >= 61 + 4 = 65
+    bytes), 2 from 257 (>= 261 bytes): never more than one excess byte per 65 bytes covered. The last
+    literal stands alone and costs at most 3 over its data."""
+    return n + n // 65 + 3
+
+
+def compressor_errors(stream, n):
+    """[violation, ...] of the compressor's grammar in `stream`, the compressed form of n bytes."""
+    try:
+        declared, toks = parse(stream)
+    except ValueError as e:
+        return [f"not a Snappy stream: {e}"]
+    errs = []
+    if declared != n:
+        errs.append(f"declares {declared} bytes for {n}")
+    pre = toks[0][3] if toks else len(stream)
+    if bytes(stream[:pre]) != varint(n):
+        errs.append(f"preamble {bytes(stream[:pre]).hex()} is not the canonical varint of {n}")
+    per_job = {}
+    for (kind, off, ln, at, op), size in zip(toks, token_sizes(stream, toks)):
+        j = op // JOB
+        per_job[j] = per_job.get(j, 0) + size
+        where = f"token at input byte {at} (output {op}, length {ln}, offset {off})"
+        if (op + ln - 1) // JOB != j:
+            errs.append(f"{where}: its output crosses a multiple of {JOB}")
+        if kind == LITERAL:
+            want = 1 if ln <= 60 else 2 if ln <= 256 else 3 if ln <= 65536 else 4
+            if size - ln != want:
+                errs.append(f"{where}: literal header of {size - ln} bytes, minimal is {want}")
+            continue
+        if not 4 <= ln <= 64:
+            errs.append(f"{where}: copy length outside 4..64")
+        if off < 1:
+            errs.append(f"{where}: copy offset < 1")
+        want = COPY1 if ln <= 11 and off < 2048 else COPY2
+        if kind != want:
+            errs.append(f"{where}: copy-{(1, 2, 4)[kind - 1]} where the compressor writes copy-{want}")
+        if op - off < JOB * j:
+            errs.append(f"{where}: reads before the start of its own job")
+    for j, size in sorted(per_job.items()):
+        ln = min(JOB, n - j * JOB)
+        if size > job_bound(ln):
+            errs.append(f"job {j}: {size} bytes for {ln}, bound {job_bound(ln)}")
+    return errs
+
+
+def job_slices(stream, n):
+    """[(input start, input end)] of every job's tokens in `stream` (cut where a token starts at a multiple
+    of JOB output bytes; needs a stream without compressor_errors)."""
+    _declared, toks = parse(stream)
+    starts = [t[3] for t in toks if t[4] % JOB == 0]
+    assert len(starts) == (n + JOB - 1) // JOB, "a job does not start with a token"
+    return list(zip(starts, starts[1:] + [len(stream)]))
+
+
 # ============================================================================ the valid corpus
+
+ASSEMBLED = {}      # case name -> the token list its Stream recorded (positions relative to the body)
+
 
 def _case(name, s, fb=FB_OK):
     stream, exp = s.finish()
     assert exp is not None, name
+    ASSEMBLED[name] = tuple(s.tokens)
     return (name, stream, exp, fb, frozenset(s.tags))
 
 

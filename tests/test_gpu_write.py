@@ -52,8 +52,12 @@ def test_snappy_compress_roundtrip(dec, oracle, name):
     comp = gpu_compress(dec, data)
     assert len(comp) <= 32 + len(data) + len(data) // 6
     assert oracle.snappy_uncompress(comp) == data                 # CPU restatement of the format
-    got, _fb = dec.snappy_decompress(comp, cap=max(1, len(data)))  # the GPU read path
+    got, fb = dec.snappy_decompress(comp, cap=max(1, len(data)))   # the GPU read path
     assert got == data
+    # ... on its block-parallel path (pf_snappy_par.h FB_OK): 2 (pieces re-run as one page) or 3 (serial kernel) would
+    # mean a copy across a 64 KiB mark or a token chain the index pass lost. pf_snappy_decompress runs without
+    # k_snappy_head, so the literal-only codes 4 and 5 do not occur here, not even for random_300k.
+    assert fb == 0, (name, fb)
     if len(data) >= 1000 and name not in ("random_300k",):
         assert len(comp) < 0.6 * len(data), (name, len(comp), len(data))
 
