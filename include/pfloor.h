@@ -344,7 +344,8 @@ typedef struct pf_encode_column {
                                      | 8: statistics; | 16: page CRCs */
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
-    int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's) or PF_CODEC_UNCOMPRESSED */
+    int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's), PF_CODEC_ZSTD (every page section one frame,
+                                     compressed on the GPU) or PF_CODEC_UNCOMPRESSED; others: PF_ERR_UNSUPPORTED_CODEC */
     int32_t  bloom_bytes;         /* split-block Bloom filter of the chunk's present values, filled on the GPU: its
                                      size in bytes, a power of two in [32, 128 MiB] (else PF_ERR_INVALID_ARG);
                                      0 = none, the bytes of every release before it. BOOLEAN: ignored, no filter */
@@ -365,9 +366,10 @@ typedef struct pf_encoded_chunk {
                                      PF_ENCODE_HYBRID_RUNS PF_ENC_RLE for BOOLEAN */
     int32_t  fallback;            /* 0; 1 dictionary above the limit; 2 hash collision; 3 type (BOOLEAN) */
     int32_t  codec;               /* ColumnMetaData.codec */
-    float    snappy_ms;           /* k_snappy_compress time (HIP events; 0 when stage timing is off) */
+    float    snappy_ms;           /* the compressor's time, k_snappy_compress or k_zstd_compress, whichever codec ran (the
+                                     name is older than ZSTD; HIP events; 0 when stage timing is off) */
     float    encode_ms;           /* dictionary + page (PLAIN, ids, DELTA_*, hybrid runs) kernels time (HIP events; 0 when timing is off) */
-    int64_t  snappy_in, snappy_out;    /* bytes into / out of the compressor */
+    int64_t  snappy_in, snappy_out;    /* bytes into / out of the compressor, for whichever codec ran */
     /* Chunk statistics (PF_ENCODE_STATISTICS; all zero: none). pf_writer_add_chunk writes them as
      * ColumnMetaData.statistics, and a file with any gets FileMetaData.column_orders (TYPE_ORDER). */
     int32_t  stats_flags;         /* PF_STATS_* */
@@ -393,6 +395,11 @@ int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_device, pf_
  * inside it, so tokens never cross a 64 KiB output boundary). Host buffers, synchronous;
  * *out_len = compressed length (cap >= 32 + n + n / 6 always suffices). */
 int pf_snappy_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
+/* ZSTD-compress one buffer on the GPU into one frame (RFC 8878; single segment, content size, no dictionary, no
+ * checksum): independent 8 KiB jobs, one block each (RLE, compressed with Huffman literals and the predefined
+ * sequence tables, or raw when that is not smaller). Host buffers, synchronous; *out_len = compressed length, also
+ * when it exceeds cap (PF_ERR_CAPACITY; cap >= 12 + n + 3 * (n / 8192 + 1) always suffices). */
+int pf_zstd_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
 
 /* File writer (host): "PAR1", row groups of encoded chunks, Thrift compact FileMetaData footer. */
 typedef struct pf_writer pf_writer;

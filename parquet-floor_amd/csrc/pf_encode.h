@@ -16,12 +16,20 @@ constexpr uint32_t SC_BLOCK = 8192;
 // worst case of one compressed job (literal headers of <= 3 bytes per run): Google's bound
 constexpr uint32_t SC_SLOT = ((32u + SC_BLOCK + SC_BLOCK / 6u) + 255u) & ~255u;
 
-struct SnapCJob {
+// ZSTD (pf_zstd_enc.hip): the same job geometry, one job = one block of the section's frame, written whole
+// (3-byte header included) into its slot, so a job never takes more than 3 + its length (a block that does
+// not shrink is stored raw). 8 KiB as for Snappy; larger blocks are not measured yet.
+constexpr uint32_t ZC_BLOCK = 8192;
+constexpr uint32_t ZC_SLOT = ((3u + ZC_BLOCK) + 255u) & ~255u;
+
+struct CompJob {
     const uint8_t* src;
-    uint8_t* dst;      // SC_SLOT bytes
-    uint32_t len;      // <= SC_BLOCK
-    uint32_t pad;
+    uint8_t* dst;      // SC_SLOT / ZC_SLOT bytes
+    uint32_t len;      // <= SC_BLOCK / ZC_BLOCK
+    uint32_t last;     // ZSTD: the job ends its section (Last_Block); Snappy: 0
 };
+using SnapCJob = CompJob;
+using ZstdCJob = CompJob;
 
 struct EncPage {
     uint64_t out_off;  // values section in vals_out
@@ -168,5 +176,6 @@ hipError_t enc_dictionary(const EncArgs& a, uint32_t m, int key_bits, void* temp
 void enc_dictionary_page_and_ids(const EncArgs& a, uint32_t m, hipStream_t st);
 void enc_pages(const EncArgs& a, const EncPage* d_pages, int n_pages, hipStream_t st);
 void launch_snappy_compress(const SnapCJob* d_jobs, int n_jobs, uint32_t* d_out_len, hipStream_t st);
+void launch_zstd_compress(const ZstdCJob* d_jobs, int n_jobs, uint32_t* d_out_len, hipStream_t st);
 
 }  // namespace pf

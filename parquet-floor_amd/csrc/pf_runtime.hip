@@ -26,6 +26,7 @@
 #include "pf_plan.h"
 #include "pf_snappy_par.h"
 #include "pf_xxh64.h"
+#include "pf_zstd_enc_core.h"
 #include "pfloor.h"
 
 using namespace pf;
@@ -403,22 +404,40 @@ void put_uvarint(std::vector<uint8_t>& o, uint64_t v) {
     o.push_back(uint8_t(v));
 }
 
-// Snappy-compress `sections` (device, each [off, off + len) of `base`) into SC_BLOCK-job slots;
-// returns per section the host stream (varint length + block outputs) in `streams`.
+// Bytes the host puts in front of a section's jobs: Snappy's length varint, or ZSTD's frame header (and for
+// a section of 0 bytes, which has no job, the one empty last raw block).
+size_t stream_head(int codec, uint64_t n, uint8_t* o /* 12 bytes */) {
+    if (codec == PF_CODEC_ZSTD) {
+        size_t k = zstd::frame_header_put(n, o);
+        if (n == 0) { std::memcpy(o + k, zstd::ZE_EMPTY_BLOCK, 3); k += 3; }
+        return k;
+    }
+    size_t k = 0;
+    while (n >= 0x80) { o[k++] = uint8_t(n | 0x80); n >>= 7; }
+    o[k++] = uint8_t(n);
+    return k;
+}
+
+// Compress `sections` (device, each [off, off + len) of `base`) with `codec` (PF_CODEC_SNAPPY | PF_CODEC_ZSTD)
+// into the slots of independent jobs of SC_BLOCK / ZC_BLOCK bytes; returns per section the host stream (Snappy:
+// varint length + block outputs; ZSTD: frame header + the jobs' blocks) in `streams`.
 // With `crc_out` (PF_ENCODE_PAGE_CRC): k_enc_crc right behind the compressor over every job's slot, in job
 // order, then over `extra`; the results come back in the copy that brings the jobs' lengths.
 int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::pair<uint64_t, uint64_t>>& sections,
-                      std::vector<std::vector<uint8_t>>& streams, float* kernel_ms = nullptr,
+                      std::vector<std::vector<uint8_t>>& streams, int codec, float* kernel_ms = nullptr,
                       const std::vector<CrcPiece>* extra = nullptr, std::vector<CrcOut>* crc_out = nullptr, float* crc_ms = nullptr) {
     hipStream_t st = ctx->stream;
-    std::vector<SnapCJob> jobs;
+    const bool zs = codec == PF_CODEC_ZSTD;
+    const uint32_t JOB = zs ? ZC_BLOCK : SC_BLOCK, SLOT = zs ? ZC_SLOT : SC_SLOT;
+    std::vector<CompJob> jobs;
     std::vector<std::pair<size_t, size_t>> range(sections.size());   // jobs of each section
     for (size_t i = 0; i < sections.size(); i++) {
         range[i].first = jobs.size();
-        for (uint64_t o = 0; o < sections[i].second; o += SC_BLOCK) {
-            SnapCJob j{};
+        for (uint64_t o = 0; o < sections[i].second; o += JOB) {
+            CompJob j{};
             j.src = base + sections[i].first + o;
-            j.len = uint32_t(std::min<uint64_t>(SC_BLOCK, sections[i].second - o));
+            j.len = uint32_t(std::min<uint64_t>(JOB, sections[i].second - o));
+            j.last = zs && o + j.len == sections[i].second;
             jobs.push_back(j);
         }
         range[i].second = jobs.size();
@@ -426,32 +445,32 @@ int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::p
     const size_t nj = jobs.size();
     size_t m = 0;
     auto take = [](size_t& cur, size_t sz) { size_t o = align_up(cur, 256); cur = o + sz; return o; };
-    const size_t o_jobs = take(m, sizeof(SnapCJob) * std::max<size_t>(nj, 1));
+    const size_t o_jobs = take(m, sizeof(CompJob) * std::max<size_t>(nj, 1));
     // the jobs' lengths and, behind them, the pieces' CRCs: one D2H
     const size_t np = crc_out ? nj + (extra ? extra->size() : 0) : 0;
     const size_t o_crc_in_len = align_up(4 * nj, 16);
     const size_t len_bytes = np ? o_crc_in_len + sizeof(CrcOut) * np : 4 * std::max<size_t>(nj, 1);
     const size_t o_len = take(m, len_bytes);
     const size_t o_pieces = take(m, sizeof(CrcPiece) * std::max<size_t>(np, 1));
-    const size_t o_slots = take(m, size_t(SC_SLOT) * std::max<size_t>(nj, 1));
+    const size_t o_slots = take(m, size_t(SLOT) * std::max<size_t>(nj, 1));
     HIPCHK(ctx, ctx->d_enc_out.ensure(m));
     uint8_t* d = static_cast<uint8_t*>(ctx->d_enc_out.p);
-    for (size_t k = 0; k < nj; k++) jobs[k].dst = d + o_slots + k * SC_SLOT;
+    for (size_t k = 0; k < nj; k++) jobs[k].dst = d + o_slots + k * SLOT;
     // compressed lengths + slots come back into the context's pinned staging (no zero-fill, DMA speed)
-    HIPCHK(ctx, ctx->h_enc_slots.ensure(align_up(len_bytes, 256) + nj * size_t(SC_SLOT)));
+    HIPCHK(ctx, ctx->h_enc_slots.ensure(align_up(len_bytes, 256) + nj * size_t(SLOT)));
     uint32_t* lens = static_cast<uint32_t*>(ctx->h_enc_slots.p);
     uint8_t* slots = static_cast<uint8_t*>(ctx->h_enc_slots.p) + align_up(len_bytes, 256);
     std::vector<CrcPiece> pieces(np);
     if (nj) {
-        HIPCHK(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(SnapCJob) * nj, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(CompJob) * nj, hipMemcpyHostToDevice, st));
         EVREC(ctx, ctx->ev[0], st);
-        launch_snappy_compress(reinterpret_cast<const SnapCJob*>(d + o_jobs), int(nj), reinterpret_cast<uint32_t*>(d + o_len), st);
+        (zs ? launch_zstd_compress : launch_snappy_compress)(reinterpret_cast<const CompJob*>(d + o_jobs), int(nj), reinterpret_cast<uint32_t*>(d + o_len), st);
         HIPCHK(ctx, hipGetLastError());
         EVREC(ctx, ctx->ev[1], st);
     }
     if (np) {
         const uint32_t* d_len = reinterpret_cast<const uint32_t*>(d + o_len);
-        for (size_t k = 0; k < nj; k++) pieces[k] = CrcPiece{jobs[k].dst, d_len + k, 0u, SC_SLOT};
+        for (size_t k = 0; k < nj; k++) pieces[k] = CrcPiece{jobs[k].dst, d_len + k, 0u, SLOT};
         for (size_t k = nj; k < np; k++) pieces[k] = (*extra)[k - nj];
         HIPCHK(ctx, hipMemcpyAsync(d + o_pieces, pieces.data(), sizeof(CrcPiece) * np, hipMemcpyHostToDevice, st));
         EVREC(ctx, ctx->ev[8], st);
@@ -460,7 +479,7 @@ int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::p
         EVREC(ctx, ctx->ev[9], st);
     }
     if (nj || np) HIPCHK(ctx, hipMemcpyAsync(lens, d + o_len, np ? len_bytes : 4 * nj, hipMemcpyDeviceToHost, st));
-    if (nj) HIPCHK(ctx, hipMemcpyAsync(slots, d + o_slots, nj * size_t(SC_SLOT), hipMemcpyDeviceToHost, st));
+    if (nj) HIPCHK(ctx, hipMemcpyAsync(slots, d + o_slots, nj * size_t(SLOT), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (crc_out) {
         const CrcOut* h = reinterpret_cast<const CrcOut*>(reinterpret_cast<const uint8_t*>(lens) + o_crc_in_len);
@@ -477,10 +496,11 @@ int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::p
     streams.assign(sections.size(), {});
     for (size_t i = 0; i < sections.size(); i++) {
         std::vector<uint8_t>& o = streams[i];
-        put_uvarint(o, sections[i].second);
+        uint8_t head[12];
+        o.assign(head, head + stream_head(codec, sections[i].second, head));
         for (size_t k = range[i].first; k < range[i].second; k++) {
-            if (lens[k] > SC_SLOT) return fail(ctx, PF_ERR_HIP, "snappy compress: block overflow");
-            const uint8_t* b = slots + k * size_t(SC_SLOT);
+            if (lens[k] > (zs ? 3 + jobs[k].len : SLOT)) return fail(ctx, PF_ERR_HIP, zs ? "zstd compress: block overflow" : "snappy compress: block overflow");
+            const uint8_t* b = slots + k * size_t(SLOT);
             o.insert(o.end(), b, b + lens[k]);
         }
     }
@@ -498,10 +518,28 @@ extern "C" int pf_snappy_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uin
     HIPCHK(ctx, ctx->d_enc.ensure(std::max<size_t>(n, 1)));
     if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_enc.p, src, n, hipMemcpyHostToDevice, ctx->stream));
     std::vector<std::vector<uint8_t>> streams;
-    const int rc = compress_sections(ctx, static_cast<const uint8_t*>(ctx->d_enc.p), {{0, n}}, streams);
+    const int rc = compress_sections(ctx, static_cast<const uint8_t*>(ctx->d_enc.p), {{0, n}}, streams, PF_CODEC_SNAPPY);
     if (rc) return rc;
     *out_len = streams[0].size();
     if (streams[0].size() > cap) return fail(ctx, PF_ERR_CAPACITY, "snappy: destination too small");
+    std::memcpy(dst, streams[0].data(), streams[0].size());
+    return PF_OK;
+}
+
+extern "C" int pf_zstd_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len) {
+    if (!ctx || (!src && n) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+    if (n > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "zstd: buffer too large");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
+    ctx->copies_pending = false;
+    HIPCHK(ctx, ctx->d_enc.ensure(std::max<size_t>(n, 1)));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_enc.p, src, n, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<std::vector<uint8_t>> streams;
+    const int rc = compress_sections(ctx, static_cast<const uint8_t*>(ctx->d_enc.p), {{0, n}}, streams, PF_CODEC_ZSTD);
+    if (rc) return rc;
+    *out_len = streams[0].size();
+    if (streams[0].size() > cap) return fail(ctx, PF_ERR_CAPACITY, "zstd: destination too small");
     std::memcpy(dst, streams[0].data(), streams[0].size());
     return PF_OK;
 }
@@ -514,8 +552,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         return fail(ctx, PF_ERR_UNSUPPORTED_TYPE, "encode: unsupported physical type");
     const int64_t n = col->num_rows;
     if (n < 0 || n > 0x7ffffff0 || (col->max_def != 0 && col->max_def != 1)) return fail(ctx, PF_ERR_INVALID_ARG, "encode: bad shape");
-    if (col->codec != PF_CODEC_SNAPPY && col->codec != PF_CODEC_UNCOMPRESSED)
-        return fail(ctx, PF_ERR_UNSUPPORTED_CODEC, "encode: codec must be SNAPPY or UNCOMPRESSED");
+    if (col->codec != PF_CODEC_SNAPPY && col->codec != PF_CODEC_ZSTD && col->codec != PF_CODEC_UNCOMPRESSED)
+        return fail(ctx, PF_ERR_UNSUPPORTED_CODEC, "encode: codec must be SNAPPY, ZSTD or UNCOMPRESSED");
+    const bool compressed = col->codec != PF_CODEC_UNCOMPRESSED;
     if (col->bloom_bytes != 0 && (col->bloom_bytes < 0 || !bloom_size_ok(uint64_t(col->bloom_bytes))))
         return fail(ctx, PF_ERR_INVALID_ARG, "encode: bloom_bytes must be a power of two in [32, 128 MiB]");
     const size_t bloom = pt == PF_BOOLEAN ? 0 : size_t(col->bloom_bytes);   // BOOLEAN: no filter (parquet-mr builds none)
@@ -917,9 +956,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     std::vector<uint8_t> hlv(lv_total);   // hybrid runs: the pages' levels
     float snap_ms = 0.f, crc_ms = 0.f;
     // Page CRCs (PF_ENCODE_PAGE_CRC): the pieces of the pages that lie in device memory -- the compression jobs'
-    // slots (SNAPPY; compress_sections lists them) or the sections themselves, and the levels: the stream the GPU
+    // slots (SNAPPY, ZSTD; compress_sections lists them) or the sections themselves, and the levels: the stream the GPU
     // encoded (hybrid runs), or the whole validity bytes of the page's rows, which the one bit-packed run repeats
-    // -- go through k_enc_crc; `crcs` holds the jobs (SNAPPY) or sections first, then the levels.
+    // -- go through k_enc_crc; `crcs` holds the jobs (SNAPPY, ZSTD) or sections first, then the levels.
     std::vector<CrcPiece> lv_pieces;
     std::vector<CrcOut> crcs;
     std::vector<int> lv_piece(pp.size(), -1);   // the page's whole level stream
@@ -937,9 +976,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             }
         }
     size_t crc_first_lv = 0;   // index of the first level stream in crcs
-    if (col->codec == PF_CODEC_SNAPPY) {
+    if (compressed) {
         if (lv_total) HIPCHK(ctx, hipMemcpyAsync(hlv.data(), SEC + o_lv, lv_total, hipMemcpyDeviceToHost, st));
-        const int rc = compress_sections(ctx, SEC, sections, bodies, &snap_ms, &lv_pieces, want_crc ? &crcs : nullptr, &crc_ms);
+        const int rc = compress_sections(ctx, SEC, sections, bodies, col->codec, &snap_ms, &lv_pieces, want_crc ? &crcs : nullptr, &crc_ms);
         if (rc) return rc;
         if (want_crc) crc_first_lv = crcs.size() - lv_pieces.size();
     } else {
@@ -976,8 +1015,8 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     int64_t unc = 0;
     size_t bi = 0;
     // CRC of a page: its pieces folded in stored order (pf_crc.h); the bytes the host generates itself (the
-    // length varint, a bit-packed level run built from hval) are fed bytewise.
-    size_t crc_job = 0;   // SNAPPY: the next job in crcs
+    // length varint or the frame header, a bit-packed level run built from hval) are fed bytewise.
+    size_t crc_job = 0;   // SNAPPY, ZSTD: the next job in crcs
     bool crc_bad = false;
     auto page_crc = [&](size_t sec, size_t page, const std::vector<uint8_t>& def) {
         uint32_t raw = 0;
@@ -997,11 +1036,13 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
             raw = crc_raw_bytes(raw, def.data(), def.size());
             len += def.size();
         }
-        if (col->codec == PF_CODEC_SNAPPY) {
-            const size_t vl = uvarint_len(sections[sec].second);
+        if (compressed) {
+            uint8_t head[12];
+            const size_t vl = stream_head(col->codec, sections[sec].second, head);
             raw = crc_raw_bytes(raw, bodies[sec].data(), vl);
             len += vl;
-            for (uint64_t o = 0; o < sections[sec].second; o += SC_BLOCK) piece(crcs[crc_job++]);
+            const uint32_t job = col->codec == PF_CODEC_ZSTD ? ZC_BLOCK : SC_BLOCK;
+            for (uint64_t o = 0; o < sections[sec].second; o += job) piece(crcs[crc_job++]);
         } else {
             piece(crcs[sec]);
         }
@@ -1072,7 +1113,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         h.num_rows = int32_t(rows);
         h.encoding = data_enc;
         h.def_bytes = int32_t(def.size());
-        h.is_compressed = col->codec == PF_CODEC_SNAPPY;
+        h.is_compressed = compressed;
         if (want_crc) { h.has_crc = true; h.crc = page_crc(bi, i, def); }
         h.stats = stats_of(i, rows - p.cnt);
         const size_t h0 = o.size();
@@ -1123,7 +1164,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     if (bloom && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&out->bloom_ms, ctx->ev_bloom[0], ctx->ev_bloom[1]));
     out->snappy_in = 0;
     out->snappy_out = 0;
-    if (col->codec == PF_CODEC_SNAPPY)
+    if (compressed)
         for (size_t i = 0; i < sections.size(); i++) {
             out->snappy_in += int64_t(sections[i].second);
             out->snappy_out += int64_t(bodies[i].size());

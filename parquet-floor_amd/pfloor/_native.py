@@ -158,6 +158,7 @@ def _load(path):
         "pf_file_last_error": ([], C.c_char_p),
         "pf_encode_chunk": ([vp, vp, i32, vp], C.c_int),
         "pf_snappy_compress": ([vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)], C.c_int),
+        "pf_zstd_compress": ([vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)], C.c_int),
         "pf_writer_open": ([C.c_char_p, vp, i32, C.POINTER(vp)], C.c_int),
         "pf_writer_add_chunk": ([vp, i32, vp], C.c_int),
         "pf_writer_end_row_group": ([vp, C.c_int64], C.c_int),

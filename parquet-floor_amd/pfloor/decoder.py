@@ -215,6 +215,18 @@ class GpuDecoder:
             return rc
         return dst[:size].tobytes() if out_len.value == size else -2
 
+    def zstd_compress(self, data: bytes, cap=None):
+        """bytes -> one ZSTD frame, compressed on the GPU (k_zstd_compress). Returns the frame, or a negative
+        status (-6: cap is too small). cap: the destination's size (default: what always suffices)."""
+        src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+        out_len = C.c_size_t()
+        cap = cap if cap is not None else 12 + len(data) + 3 * (len(data) // 8192 + 1)
+        dst = np.zeros(max(1, cap), dtype=np.uint8)
+        rc = lib().pf_zstd_compress(self.h, src.ctypes.data, len(data), dst.ctypes.data, cap, C.byref(out_len))
+        if rc != 0:
+            return rc
+        return dst[:out_len.value].tobytes()
+
     def scan_pages(self, data, chunks, verify_crc=False, page_cap=4096):
         """GPU page-header scan (pf_scan_pages) of column chunks in one host buffer.
         chunks: [(chunk_offset, chunk_size, num_values)]. Returns (rc, [(status, err_page, crc_pages,

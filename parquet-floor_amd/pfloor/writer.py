@@ -9,6 +9,11 @@ row group on the host (dehydrated column by column, SimpleWriteSupport.writeFiel
 each column chunk is encoded on the GPU (pf_encode_chunk: dictionary build, ids, PLAIN or DELTA_*
 values, Snappy), then appended with its page headers by the host file writer (pf_writer_*).
 
+codec=ZSTD (ParquetWriter(..., codec=ZSTD), PF_CODEC_ZSTD) compresses every page section into one ZSTD frame on
+the GPU instead (k_zstd_compress: 8 KiB blocks, Huffman literals, the predefined sequence tables), the codec most
+engines write today; codec=UNCOMPRESSED stores the sections as they are. The default stays SNAPPY, and every
+option below combines with every codec.
+
 The fallback encoding is PLAIN by default. With delta_fallback=True a chunk that is not
 dictionary-encoded is written as parquet-mr's v2 writer writes it: DELTA_BINARY_PACKED (INT32,
 INT64) or DELTA_BYTE_ARRAY (BINARY) data pages, encoded on the GPU in parquet-mr's stream layout;
@@ -51,6 +56,7 @@ from . import _native
 from ._native import PfError, check, lib
 
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1, 2, 3, 4, 5, 6, 7
+UNCOMPRESSED, SNAPPY, ZSTD = 0, 1, 6   # pf_encode_column.codec (PF_CODEC_*): the codecs the write path has
 ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK, ENCODE_HYBRID_RUNS = 1, 2, 4   # pf_encode_column.dictionary bits (PF_ENCODE_*)
 ENCODE_STATISTICS, ENCODE_PAGE_CRC = 8, 16
 STATS_NULL_COUNT, STATS_MIN_MAX = 1, 2   # pf_encoded_chunk.stats_flags (PF_STATS_*)
@@ -289,12 +295,13 @@ class ParquetWriter:
     row_group_rows bounds the rows buffered per row group (parquet-mr flushes by its 128 MiB
     block size; the bound here is in rows, the byte size of a row group is the caller's)."""
 
-    def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=1,
+    def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=SNAPPY,
                  decoders=None, delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False,
                  bloom_filters=None, bloom_fpp=0.01, bloom_max_bytes=1 << 20):
         """bloom_filters: {field name: expected distinct count | True (bloom_max_bytes) | {"bytes": n}}, the columns
         that get a Bloom filter, sized by bloom_optimal_bytes(ndv, bloom_fpp, bloom_max_bytes) (see above); an unknown
         name is a ValueError, a BOOLEAN field gets none.
+        codec: SNAPPY (the default), ZSTD or UNCOMPRESSED; any other is refused (PF_ERR_UNSUPPORTED_CODEC).
         delta_fallback: chunks that are not dictionary-encoded get DELTA_* data pages (see above).
         hybrid_runs: ids, definition levels and BOOLEAN values in parquet-mr's hybrid run shape (see above).
         statistics: page and chunk Statistics and the footer's column_orders (see above).
@@ -478,4 +485,4 @@ class ParquetWriter:
 
 
 __all__ = ["ParquetWriter", "bloom_optimal_bytes", "MessageType", "Field", "Dehydrator", "ValueWriter", "required", "optional",
-           "BOOLEAN", "INT32", "INT64", "FLOAT", "DOUBLE", "BINARY", "_native"]
+           "BOOLEAN", "INT32", "INT64", "FLOAT", "DOUBLE", "BINARY", "UNCOMPRESSED", "SNAPPY", "ZSTD", "_native"]
