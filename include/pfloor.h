@@ -293,6 +293,31 @@ int pf_file_read(pf_file* f, uint64_t offset, uint64_t size, void* dst);
  * if it has none; *length = bloom_filter_length (header + bitset), -1 if the writer left it out (parquet-mr 1.12: read
  * the header for numBytes). PF_ERR_IO if either points outside the file. */
 int pf_file_chunk_bloom(pf_file* f, int row_group, int column, int64_t* offset, int32_t* length);
+/* The chunk's page index (host only, no context). Ranges in the file: ColumnChunk column_index_offset / _length and
+ * offset_index_offset / _length; -1 where absent. PF_ERR_IO if a range leaves the file. */
+int pf_file_chunk_index_ranges(pf_file* f, int row_group, int column, int64_t* ci_off, int32_t* ci_len,
+                               int64_t* oi_off, int32_t* oi_len);
+typedef struct pf_page_location {
+    int64_t offset;               /* file offset of the page header */
+    int32_t compressed_page_size; /* header + stored body */
+    int64_t first_row_index;      /* within the row group */
+} pf_page_location;
+/* OffsetIndex.page_locations: *n = their number (also when it exceeds cap: PF_ERR_CAPACITY, the first cap are written);
+ * out may be NULL with cap 0. PF_ERR_STATE if the chunk has no OffsetIndex; PF_ERR_CORRUPT_PAGE if the struct is
+ * damaged (a varint overrun, a size past the range); never an out-of-bounds read. Unknown fields are skipped. */
+int pf_file_offset_index(pf_file* f, int row_group, int column, pf_page_location* out, int cap, int* n);
+typedef struct pf_column_index {
+    int32_t n_pages;
+    int32_t boundary_order;       /* 0 UNORDERED, 1 ASCENDING, 2 DESCENDING */
+    const uint8_t* null_pages;    /* n_pages bytes, 0 / 1 */
+    const int64_t* null_counts;   /* n_pages, or NULL when the writer left them out */
+    const uint8_t* values;        /* min and max of every page, back to back */
+    const uint32_t* value_off;    /* 2 * n_pages + 1: page p's min is [off[2p], off[2p+1]), its max [off[2p+1], off[2p+2]) */
+} pf_column_index;
+/* ColumnIndex; the arrays are owned by the pf_file (valid until it is closed). PF_ERR_STATE if the chunk has none;
+ * PF_ERR_CORRUPT_PAGE if the struct is damaged (list lengths that disagree, a varint overrun, a size past the
+ * range). Unknown fields (the level histograms) are skipped. */
+int pf_file_column_index(pf_file* f, int row_group, int column, pf_column_index* out);
 const char* pf_file_created_by(pf_file* f);
 
 /* ---- write path: the reference's ParquetWriter (ParquetWriter.java:61-165: SNAPPY,
@@ -300,9 +325,9 @@ const char* pf_file_created_by(pf_file* f);
  *      GPU: dictionary encode (entries in first-occurrence order, like parquet-mr's
  *      DictionaryValuesWriter), RLE/bit-packed hybrid ids, PLAIN values, Snappy compression of
  *      every page. Flat schemas of the types the reference writes (ParquetWriter.java:143-157):
- *      BOOLEAN, INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY (UTF8). Opt-in, also on the GPU: statistics, page CRCs
- *      (PF_ENCODE_* bits below) and a split-block Bloom filter per chunk (pf_encode_column.bloom_bytes), which
- *      pf_writer_close stores behind the last row group. ---- */
+ *      BOOLEAN, INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY (UTF8). Opt-in, also on the GPU: statistics, page CRCs, the
+ *      page index (PF_ENCODE_* bits below) and a split-block Bloom filter per chunk (pf_encode_column.bloom_bytes);
+ *      pf_writer_close stores indexes and filters behind the last row group. ---- */
 /* pf_encode_column.dictionary is a bit set (0 and 1 keep the meaning they always had). */
 #define PF_ENCODE_DICTIONARY     1   /* dictionary-encode; the chunk falls back as a whole above
                                         dict_page_limit, on a hash collision, or for BOOLEAN */
@@ -327,6 +352,14 @@ const char* pf_file_created_by(pf_file* f);
 #define PF_ENCODE_PAGE_CRC       16  /* PageHeader.crc (CRC-32 of the compressed_page_size bytes after the
                                         header, dictionary pages included), its pieces reduced on the GPU.
                                         Clear: no crc field */
+#define PF_ENCODE_PAGE_INDEX 32      /* the chunk's page index (ColumnIndex and OffsetIndex of parquet-format's
+                                        PageIndex): per data page null_page, null_count and min / max, the boundary
+                                        order of the written values, and every page's location; built on the GPU
+                                        from the results of the statistics kernels (pf_encoded_chunk.index_*).
+                                        pf_writer_close stores them between the last row group and the Bloom filters.
+                                        Independent of PF_ENCODE_STATISTICS: alone it runs the statistics kernels but
+                                        writes no Statistics struct. Clear: no index, the bytes of every release
+                                        before it */
 #define PF_STATS_NULL_COUNT 1        /* pf_encoded_chunk.stats_flags: null_count is set */
 #define PF_STATS_MIN_MAX    2        /* stat_min / stat_max are set */
 typedef struct pf_encode_column {
@@ -341,7 +374,7 @@ typedef struct pf_encode_column {
     int32_t  dictionary;          /* PF_ENCODE_* bits; 1: dictionary-encode (PLAIN above dict_page_limit or on a
                                      hash collision), 3: the same with the DELTA_* fallback, 2: DELTA_* pages;
                                      | 4: parquet-mr's hybrid runs (7 = the encodings of its PARQUET_2_0 writer);
-                                     | 8: statistics; | 16: page CRCs */
+                                     | 8: statistics; | 16: page CRCs; | 32: page index */
     int32_t  page_rows;           /* rows per data page; 0 = 20000 (parquet-mr page.row.count.limit) */
     int32_t  dict_page_limit;     /* dictionary page bytes; 0 = 1 MiB (parquet.dictionary.page.size) */
     int32_t  codec;               /* PF_CODEC_SNAPPY (the reference's), PF_CODEC_ZSTD (every page section one frame,
@@ -349,6 +382,12 @@ typedef struct pf_encode_column {
     int32_t  bloom_bytes;         /* split-block Bloom filter of the chunk's present values, filled on the GPU: its
                                      size in bytes, a power of two in [32, 128 MiB] (else PF_ERR_INVALID_ARG);
                                      0 = none, the bytes of every release before it. BOOLEAN: ignored, no filter */
+    int32_t  index_truncate;      /* PF_ENCODE_PAGE_INDEX, BYTE_ARRAY: the longest min / max the ColumnIndex holds.
+                                     0 = 64 (parquet-mr parquet.columnindex.truncate.length), -1 = no truncation,
+                                     else in [1, 2047] (otherwise PF_ERR_INVALID_ARG). A longer min is cut to its
+                                     first T bytes; a longer max is its first T bytes less trailing 0xFF bytes with
+                                     the last byte left incremented (unsigned bytewise order; UTF-8 is not kept
+                                     valid). Ignored for the other types and with the bit clear */
 } pf_encode_column;
 
 typedef struct pf_encoded_chunk {
@@ -386,6 +425,23 @@ typedef struct pf_encoded_chunk {
                                      pf_encode_chunk, like bytes */
     int32_t  bloom_len;
     float    bloom_ms;            /* the filter's zeroing and k_enc_bloom (HIP events; 0 when timing is off); not in encode_ms */
+    /* Page index (PF_ENCODE_PAGE_INDEX; all zero / NULL with the bit clear). Arrays are owned by the ctx and valid until
+     * its next pf_encode_chunk, like bytes. pf_writer_add_chunk copies them. */
+    int32_t  index_pages;         /* = n_data_pages */
+    const int64_t* page_offset;   /* OffsetIndex: every data page's header, relative to bytes */
+    const int32_t* page_size;     /* header + stored body */
+    const int64_t* page_first_row;
+    int32_t  column_index;        /* 1: a ColumnIndex follows. 0: none (the OffsetIndex is written all the same): a page has
+                                     present values but no min / max (FLOAT / DOUBLE, all NaN), a BYTE_ARRAY max cannot be
+                                     truncated (its first T bytes are all 0xFF), or, with index_truncate = -1, an entry has
+                                     len(min) + len(max) >= 4096. index_values / index_value_off are then NULL */
+    int32_t  boundary_order;      /* 0 UNORDERED, 1 ASCENDING, 2 DESCENDING: over the written (truncated) min and max of the
+                                     pages that are not null pages; ties and a single such page are ASCENDING, none UNORDERED */
+    const uint8_t* index_null_pages;    /* one byte per page: 1 = the page has no present value */
+    const int64_t* index_null_counts;
+    const uint8_t* index_values;        /* the pages' min and max, PLAIN bytes (BYTE_ARRAY: no length prefix), back to back */
+    const uint32_t* index_value_off;    /* 2 * index_pages + 1: page p's min is [off[2p], off[2p+1]), its max
+                                           [off[2p+1], off[2p+2]); both empty for a null page */
 } pf_encoded_chunk;
 
 /* Encode one column chunk on the context's GPU. Inputs are host memory (copied) unless
@@ -411,12 +467,19 @@ typedef struct pf_write_field {
 } pf_write_field;
 int pf_writer_open(const char* path, const pf_write_field* fields, int n_fields, pf_writer** out);
 /* Append the chunk of field `field` (fields in schema order) to the current row group. A Bloom filter
- * (bloom_len > 0: a power of two >= 32, bloom not null, else PF_ERR_INVALID_ARG) is copied and kept until close. */
+ * (bloom_len > 0: a power of two >= 32, bloom not null, else PF_ERR_INVALID_ARG) is copied and kept until close,
+ * and so is a page index (index_pages > 0: page_offset, page_size, page_first_row, index_null_pages and
+ * index_null_counts not null; column_index = 1: index_values and index_value_off not null and the offsets
+ * non-decreasing; else PF_ERR_INVALID_ARG). */
 int pf_writer_add_chunk(pf_writer* w, int field, const pf_encoded_chunk* chunk);
 int pf_writer_end_row_group(pf_writer* w, int64_t num_rows);
-/* Bloom filters (BloomFilterHeader {1 numBytes, 2 BLOCK, 3 XXHASH, 4 UNCOMPRESSED} + bitset each, in row-group then
- * column order, behind the last row group, where parquet-mr 1.12 and pyarrow put them; ColumnMetaData
- * bloom_filter_offset 14 / bloom_filter_length 15), then the footer; frees w (also on error). */
+/* Behind the last row group, in the order of parquet-mr 1.12's ParquetFileWriter.end(): every ColumnIndex
+ * {1 null_pages, 2 min_values, 3 max_values, 4 boundary_order, 5 null_counts} in row-group then column order, every
+ * OffsetIndex {1 page_locations {1 offset, 2 compressed_page_size, 3 first_row_index}} in the same order (ColumnChunk
+ * offset_index_offset 4 / offset_index_length 5 / column_index_offset 6 / column_index_length 7; a file with any
+ * ColumnIndex declares column_orders), the Bloom filters (BloomFilterHeader {1 numBytes, 2 BLOCK, 3 XXHASH,
+ * 4 UNCOMPRESSED} + bitset each, same order; ColumnMetaData bloom_filter_offset 14 / bloom_filter_length 15), then the
+ * footer; frees w (also on error). A file without indexed chunks keeps the bytes it always had. */
 int pf_writer_close(pf_writer* w);
 const char* pf_writer_last_error(void);
 const char* pf_file_last_error(void);            /* thread-local message of the last pf_file_* error */

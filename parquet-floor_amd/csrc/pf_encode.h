@@ -153,6 +153,32 @@ struct StatArgs {
 
 void enc_stats(const EncArgs& a, const StatArgs& s, hipStream_t st);
 
+// ---- page index (pf_enc_pgindex.hip; PF_ENCODE_PAGE_INDEX) ----
+constexpr uint32_t PX_NO_TRUNC = 0xffffffffu;   // PgIndexArgs::trunc: BYTE_ARRAY values are written whole
+
+// The ColumnIndex lists of one chunk, from the page results k_enc_stats_combine left in StatArgs::out. The
+// outputs are one block of the arena (the host copies it back in one piece): head, null_counts, off, null_pages, values.
+struct PgIndexHead {
+    uint32_t valid;                  // 1: a ColumnIndex can be written
+    uint32_t order;                  // 0 UNORDERED, 1 ASCENDING, 2 DESCENDING
+    uint32_t value_bytes;            // = off[2 * n_pages]
+    uint32_t non_null;               // pages with a present value
+};
+struct PgIndexArgs {
+    const StatPart* pages;           // n_pages page results
+    const uint32_t* rows;            // n_pages: rows of a page
+    const uint32_t* cnt;             // n_pages: its present values
+    uint32_t n_pages, trunc;         // trunc: longest BYTE_ARRAY entry, or PX_NO_TRUNC
+    uint32_t value_cap;              // bytes at `values`
+    uint32_t* nn;                    // n_pages scratch: the pages that are not null pages, in order
+    PgIndexHead* head;
+    long long* null_counts;          // n_pages
+    uint32_t* off;                   // 2 * n_pages + 1
+    uint8_t* null_pages;             // n_pages
+    uint8_t* values;                 // value_cap
+};
+void enc_pgindex(const EncArgs& a, const PgIndexArgs& x, hipStream_t st);
+
 // ---- page CRCs (pf_enc_crc.hip; PF_ENCODE_PAGE_CRC) ----
 struct CrcPiece {
     const uint8_t* ptr;

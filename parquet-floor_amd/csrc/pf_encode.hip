@@ -14,6 +14,8 @@
 //                   in parquet-mr's run shape (PF_ENCODE_HYBRID_RUNS): pf_enc_hybrid.hip
 //   statistics   -> min / max of every page and of the chunk over the dense values (PF_ENCODE_STATISTICS):
 //                   pf_enc_stats.hip; PageHeader.crc from the stored pieces (PF_ENCODE_PAGE_CRC): pf_enc_crc.hip
+//   page index   -> the ColumnIndex lists from the statistics kernels' page results (PF_ENCODE_PAGE_INDEX):
+//                   pf_enc_pgindex.hip
 //   Snappy       -> k_snappy_compress: one wave per 8 KiB job (hash table of 4-byte
 //                   prefixes in LDS, 64 candidate positions per step, wave-parallel match
 //                   extension); jobs are independent, so a page's stream is the varint length

@@ -24,6 +24,7 @@ struct pf_file {
     uint64_t size = 0;
     pf::FileMeta meta;
     std::map<std::pair<int, int>, std::vector<pf_page_desc>> pages;
+    std::map<std::pair<int, int>, pf::ColumnIndexMeta> column_indexes;
 };
 
 extern "C" {
@@ -119,6 +120,79 @@ int pf_file_chunk_bloom(pf_file* f, int rg, int col, int64_t* offset, int32_t* l
         return ferr(PF_ERR_IO, "Bloom filter outside the file");
     *offset = m.bloom_offset;
     if (has_len) *length = int32_t(m.bloom_length);
+    return PF_OK;
+}
+
+int pf_file_chunk_index_ranges(pf_file* f, int rg, int col, int64_t* ci_off, int32_t* ci_len, int64_t* oi_off, int32_t* oi_len) {
+    if (!f || !ci_off || !ci_len || !oi_off || !oi_len || rg < 0 || rg >= int(f->meta.row_groups.size()) || col < 0 ||
+        col >= int(f->meta.leaves.size()))
+        return ferr(PF_ERR_INVALID_ARG, "bad index");
+    const pf::ChunkMeta& m = f->meta.row_groups[rg].columns[col];
+    *ci_off = *oi_off = -1;
+    *ci_len = *oi_len = -1;
+    auto range = [&](int64_t off, int64_t len, int64_t* o, int32_t* l) {
+        if (off == -1 && len == -1) return true;
+        if (off < 4 || len < 0 || len > INT32_MAX || uint64_t(off) + uint64_t(len) > f->size) return false;
+        *o = off;
+        *l = int32_t(len);
+        return true;
+    };
+    if (!range(m.ci_offset, m.ci_length, ci_off, ci_len) || !range(m.oi_offset, m.oi_length, oi_off, oi_len))
+        return ferr(PF_ERR_IO, "page index outside the file");
+    return PF_OK;
+}
+
+namespace {
+// The bytes of a chunk's index struct (which: 0 ColumnIndex, 1 OffsetIndex); PF_ERR_STATE when it has none.
+int index_bytes(pf_file* f, int rg, int col, int which, std::vector<uint8_t>& buf) {
+    int64_t off[2];
+    int32_t len[2];
+    int rc = pf_file_chunk_index_ranges(f, rg, col, &off[0], &len[0], &off[1], &len[1]);
+    if (rc) return rc;
+    if (off[which] < 0) return ferr(PF_ERR_STATE, which ? "the chunk has no OffsetIndex" : "the chunk has no ColumnIndex");
+    buf.resize(size_t(len[which]));
+    return pf_file_read(f, uint64_t(off[which]), uint64_t(len[which]), buf.data());
+}
+}  // namespace
+
+int pf_file_offset_index(pf_file* f, int rg, int col, pf_page_location* out, int cap, int* n) {
+    if (!n || cap < 0 || (cap > 0 && !out)) return ferr(PF_ERR_INVALID_ARG, "null arg");
+    std::vector<uint8_t> buf;
+    int rc = index_bytes(f, rg, col, 1, buf);
+    if (rc) return rc;
+    std::vector<pf_page_location> locs;
+    try {
+        pf::parse_offset_index(buf.data(), buf.size(), locs);
+    } catch (const std::exception& e) {
+        return ferr(PF_ERR_CORRUPT_PAGE, e.what());
+    }
+    if (locs.size() > size_t(INT32_MAX)) return ferr(PF_ERR_CORRUPT_PAGE, "too many page locations");
+    *n = int(locs.size());
+    for (int i = 0; i < *n && i < cap; i++) out[i] = locs[size_t(i)];
+    return *n > cap ? ferr(PF_ERR_CAPACITY, "page location buffer too small") : PF_OK;
+}
+
+int pf_file_column_index(pf_file* f, int rg, int col, pf_column_index* out) {
+    if (!out) return ferr(PF_ERR_INVALID_ARG, "null arg");
+    std::vector<uint8_t> buf;
+    int rc = index_bytes(f, rg, col, 0, buf);
+    if (rc) return rc;
+    pf::ColumnIndexMeta ci;
+    try {
+        pf::parse_column_index(buf.data(), buf.size(), ci);
+    } catch (const std::exception& e) {
+        return ferr(PF_ERR_CORRUPT_PAGE, e.what());
+    }
+    pf::ColumnIndexMeta& k = f->column_indexes[{rg, col}];
+    k = std::move(ci);
+    if (k.null_pages.empty()) k.null_pages.push_back(0);   // never a null pointer for an index that exists
+    if (k.values.empty()) k.values.push_back(0);
+    out->n_pages = int32_t((k.value_off.size() - 1) / 2);
+    out->boundary_order = k.boundary_order;
+    out->null_pages = k.null_pages.data();
+    out->null_counts = k.has_null_counts ? k.null_counts.data() : nullptr;
+    out->values = k.values.data();
+    out->value_off = k.value_off.data();
     return PF_OK;
 }
 

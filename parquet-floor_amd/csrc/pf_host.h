@@ -20,6 +20,8 @@ struct ChunkMeta {
     int64_t data_page_offset = 0, dictionary_page_offset = 0;
     bool has_dict = false;
     int64_t bloom_offset = -1, bloom_length = -1;   // ColumnMetaData 14 / 15 (-1: absent)
+    int64_t oi_offset = -1, oi_length = -1;         // ColumnChunk 4 / 5: the OffsetIndex (-1: absent)
+    int64_t ci_offset = -1, ci_length = -1;         // ColumnChunk 6 / 7: the ColumnIndex
     // ColumnChunkMetaData.getStartingPos(): the dictionary page offset when it precedes
     // the first data page, else the data page offset.
     int64_t start() const {
@@ -50,6 +52,20 @@ struct FileMeta {
     void parse_footer(const uint8_t* p, size_t n);
     static void walk_pages(const uint8_t* chunk, size_t size, const ChunkMeta& m, std::vector<pf_page_desc>& out);
 };
+
+// A chunk's ColumnIndex as pf_file_column_index returns it: page p's min is values[value_off[2p], value_off[2p+1]),
+// its max values[value_off[2p+1], value_off[2p+2]).
+struct ColumnIndexMeta {
+    int boundary_order = 0;
+    bool has_null_counts = false;
+    std::vector<uint8_t> null_pages, values;
+    std::vector<int64_t> null_counts;
+    std::vector<uint32_t> value_off;
+};
+// Parse the Thrift compact structs at [p, p + n); unknown fields are skipped. MetaError when damaged (a varint or
+// a length past the range, list lengths that disagree, a missing required field); never reads outside the range.
+void parse_column_index(const uint8_t* p, size_t n, ColumnIndexMeta& out);
+void parse_offset_index(const uint8_t* p, size_t n, std::vector<pf_page_location>& out);
 
 // Statistics of a page or a chunk as the write path serialises them (parquet.thrift Statistics: 3 null_count,
 // 5 max_value, 6 min_value; the legacy 1 max / 2 min only where `legacy` says so).

@@ -149,7 +149,11 @@ ChunkMeta read_column_chunk(ThriftReader& r) {
     ChunkMeta m;
     int last = 0, id, t;
     while (r.field(last, id, t)) {
-        if (id == 3 && t == 12) {
+        if (id == 4) m.oi_offset = r.integer(t);
+        else if (id == 5) m.oi_length = r.integer(t);
+        else if (id == 6) m.ci_offset = r.integer(t);
+        else if (id == 7) m.ci_length = r.integer(t);
+        else if (id == 3 && t == 12) {
             int l2 = 0, i2, t2;
             while (r.field(l2, i2, t2)) {
                 switch (i2) {
@@ -236,6 +240,107 @@ void FileMeta::parse_footer(const uint8_t* p, size_t n) {
     walk(0, Frame{0, 0, 0, 0, "", ""});
     for (auto& rg : row_groups)
         if (rg.columns.size() != leaves.size()) ThriftReader::fail("row group column count");
+}
+
+// ColumnIndex: 1 null_pages list<bool>, 2 min_values list<binary>, 3 max_values list<binary>, 4 boundary_order,
+// 5 null_counts list<i64> (optional); anything else (the level histograms) is skipped. Every list element takes at
+// least one byte, so a count above the bytes left is damage, and nothing is allocated for it.
+void parse_column_index(const uint8_t* p, size_t n, ColumnIndexMeta& out) {
+    ThriftReader r{p, p + n};
+    out = ColumnIndexMeta{};
+    std::vector<std::pair<const uint8_t*, uint32_t>> lists[2];
+    bool have[6] = {};
+    int last = 0, id, t;
+    auto count = [&](int want_a, int want_b) {
+        int et;
+        const uint64_t cnt = r.list(et);
+        if (et != want_a && et != want_b) ThriftReader::fail("page index list type");
+        if (cnt > uint64_t(r.end - r.p)) ThriftReader::fail("page index list longer than the struct");
+        return size_t(cnt);
+    };
+    while (r.field(last, id, t)) {
+        if (id >= 1 && id <= 5 && have[id]) ThriftReader::fail("page index field twice");
+        if (id == 1 && t == 9) {
+            const size_t cnt = count(1, 2);
+            out.null_pages.resize(cnt);
+            for (size_t i = 0; i < cnt; i++) out.null_pages[i] = r.byte() == 1;
+            have[1] = true;
+        } else if ((id == 2 || id == 3) && t == 9) {
+            const size_t cnt = count(8, 8);
+            auto& L = lists[id - 2];
+            L.reserve(cnt);
+            for (size_t i = 0; i < cnt; i++) {
+                const uint64_t len = r.uvarint();
+                if (uint64_t(r.end - r.p) < len) ThriftReader::fail("truncated page index value");
+                L.push_back({r.p, uint32_t(len)});
+                r.p += len;
+            }
+            have[id] = true;
+        } else if (id == 4) {
+            const int64_t v = r.integer(t);
+            if (v < 0 || v > 2) ThriftReader::fail("boundary_order");
+            out.boundary_order = int(v);
+            have[4] = true;
+        } else if (id == 5 && t == 9) {
+            const size_t cnt = count(6, 6);
+            out.null_counts.resize(cnt);
+            for (size_t i = 0; i < cnt; i++) out.null_counts[i] = r.zigzag();
+            have[5] = out.has_null_counts = true;
+        } else r.skip(t);
+    }
+    if (!have[1] || !have[2] || !have[3] || !have[4]) ThriftReader::fail("page index: a required field is missing");
+    const size_t np = out.null_pages.size();
+    if (lists[0].size() != np || lists[1].size() != np || (have[5] && out.null_counts.size() != np))
+        ThriftReader::fail("page index lists differ in length");
+    uint64_t total = 0;
+    for (int k = 0; k < 2; k++)
+        for (const auto& v : lists[k]) total += v.second;
+    if (total > n) ThriftReader::fail("page index values longer than the struct");   // (so the offsets fit 32 bits: n does)
+    out.values.reserve(size_t(total));
+    out.value_off.reserve(2 * np + 1);
+    for (size_t i = 0; i < np; i++)
+        for (int k = 0; k < 2; k++) {
+            out.value_off.push_back(uint32_t(out.values.size()));
+            out.values.insert(out.values.end(), lists[k][i].first, lists[k][i].first + lists[k][i].second);
+        }
+    out.value_off.push_back(uint32_t(out.values.size()));
+}
+
+// OffsetIndex: 1 page_locations list<PageLocation {1 offset, 2 compressed_page_size, 3 first_row_index}>; anything
+// else (unencoded_byte_array_data_bytes) is skipped.
+void parse_offset_index(const uint8_t* p, size_t n, std::vector<pf_page_location>& out) {
+    ThriftReader r{p, p + n};
+    out.clear();
+    bool have = false;
+    int last = 0, id, t;
+    while (r.field(last, id, t)) {
+        if (id == 1 && t == 9) {
+            if (have) ThriftReader::fail("page locations twice");
+            have = true;
+            int et;
+            const uint64_t cnt = r.list(et);
+            if (et != 12) ThriftReader::fail("page location list type");
+            if (cnt > uint64_t(r.end - r.p)) ThriftReader::fail("page location list longer than the struct");
+            out.reserve(size_t(cnt));
+            for (uint64_t i = 0; i < cnt; i++) {
+                pf_page_location L{};
+                int seen = 0, l2 = 0, i2, t2;
+                while (r.field(l2, i2, t2)) {
+                    if (i2 == 1) { L.offset = r.integer(t2); seen |= 1; }
+                    else if (i2 == 2) {
+                        const int64_t v = r.integer(t2);
+                        if (v < 0 || v > INT32_MAX) ThriftReader::fail("page location size");
+                        L.compressed_page_size = int32_t(v);
+                        seen |= 2;
+                    } else if (i2 == 3) { L.first_row_index = r.integer(t2); seen |= 4; }
+                    else r.skip(t2);
+                }
+                if (seen != 7 || L.offset < 0 || L.first_row_index < 0) ThriftReader::fail("page location fields");
+                out.push_back(L);
+            }
+        } else r.skip(t);
+    }
+    if (!have) ThriftReader::fail("offset index without page locations");
 }
 
 // Page headers of one chunk: parquet-mr Chunk.readAllPages reads pages until the chunk's

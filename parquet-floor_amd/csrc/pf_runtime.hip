@@ -194,6 +194,9 @@ struct pf_ctx {
     bool meta_by_kernel = false;   // this batch's metadata went up by k_upload (which also zeroes bits / npub)
     uint64_t chars_need = 0;
     int reruns = 0;
+    HostBuf h_enc_px;                      // pf_encode_chunk: the page index block D2H (pf_encoded_chunk.index_*)
+    std::vector<int64_t> h_enc_pgoff, h_enc_pgrow;   // pf_encoded_chunk.page_offset / page_first_row
+    std::vector<int32_t> h_enc_pgsize;               // pf_encoded_chunk.page_size
 };
 
 namespace {
@@ -559,6 +562,11 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         return fail(ctx, PF_ERR_INVALID_ARG, "encode: bloom_bytes must be a power of two in [32, 128 MiB]");
     const size_t bloom = pt == PF_BOOLEAN ? 0 : size_t(col->bloom_bytes);   // BOOLEAN: no filter (parquet-mr builds none)
     const bool str = pt == PF_BYTE_ARRAY;
+    const bool want_index = (col->dictionary & PF_ENCODE_PAGE_INDEX) != 0;
+    if (want_index && str && col->index_truncate != 0 && col->index_truncate != -1 &&
+        (col->index_truncate < 1 || col->index_truncate > 2047))
+        return fail(ctx, PF_ERR_INVALID_ARG, "encode: index_truncate must be 0, -1 or in [1, 2047]");
+    const uint32_t px_trunc = col->index_truncate == -1 ? PX_NO_TRUNC : col->index_truncate == 0 ? 64u : uint32_t(col->index_truncate);
     if (n > 0 && (str ? (!col->offsets || (!col->chars && col->chars_len > 0) || col->chars_len < 0 || col->chars_len > 0x7fffffff)
                       : !col->values))
         return fail(ctx, PF_ERR_INVALID_ARG, "encode: missing input arrays");
@@ -636,9 +644,10 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     // statistics (PF_ENCODE_STATISTICS): a workgroup per (page, tile of ST_TILE present values)
     const bool want_stats = (col->dictionary & PF_ENCODE_STATISTICS) != 0;
     const bool want_crc = (col->dictionary & PF_ENCODE_PAGE_CRC) != 0;
+    const bool run_stats = want_stats || want_index;   // the page index is built from the statistics kernels' page results
     std::vector<StatTile> stiles;
     std::vector<uint32_t> sptile;
-    if (want_stats) {
+    if (run_stats) {
         for (size_t i = 0; i < pp.size(); i++) {
             sptile.push_back(uint32_t(stiles.size()));
             for (uint32_t o = 0; o < pp[i].cnt; o += ST_TILE)
@@ -646,7 +655,15 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         }
         sptile.push_back(uint32_t(stiles.size()));
     }
-    const size_t n_se = want_stats ? pp.size() + 1 : 0;   // statistics entries: the pages, then the chunk
+    const size_t n_se = run_stats ? pp.size() + 1 : 0;   // statistics entries: the pages, then the chunk
+    // page index (PF_ENCODE_PAGE_INDEX): the pages' rows and present values go up, one block comes back:
+    // head | null_counts | offsets | null_pages | values (the worst case: every entry as long as it can get)
+    const size_t n_px = want_index ? pp.size() : 0;
+    const uint64_t px_entry = !str ? uint64_t(w) : px_trunc == PX_NO_TRUNC ? uint64_t(ST_LIMIT) / 2 : uint64_t(px_trunc);
+    const uint64_t px_cap = 2 * px_entry * n_px;
+    if (px_cap > 0x40000000ull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: page index values over 1 GiB (fewer pages or a shorter index_truncate)");
+    const size_t px_nc = sizeof(PgIndexHead), px_off = px_nc + 8 * n_px, px_np = px_off + 4 * (2 * n_px + 1), px_val = px_np + n_px;
+    const size_t px_bytes = want_index ? px_val + size_t(px_cap) : 0;
 
     // ---- device arena ----
     size_t a_sz = 0;
@@ -672,6 +689,7 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     const size_t o_stt = take(a_sz, sizeof(StatTile) * stiles.size()), o_stp = take(a_sz, 4 * sptile.size());
     const size_t o_spart = take(a_sz, sizeof(StatPart) * stiles.size()), o_swin = take(a_sz, str ? 8 * stiles.size() : 0);
     const size_t o_sout = take(a_sz, sizeof(StatPart) * n_se), o_sbytes = take(a_sz, str ? size_t(ST_LIMIT) * n_se : 0);
+    const size_t o_xin = take(a_sz, 8 * n_px), o_xnn = take(a_sz, 4 * n_px), o_xout = take(a_sz, px_bytes);
     size_t temp_bytes = 0;
     HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
     const size_t o_temp = take(a_sz, temp_bytes);
@@ -809,8 +827,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     // Statistics: the kernels run with the page kernels (their time is in encode_ms), the results come back in
     // pinned memory with the synchronisation the bodies wait for anyway.
     const size_t st_bytes = sizeof(StatPart) * n_se + (str ? size_t(ST_LIMIT) * n_se : 0);
+    std::vector<uint32_t> px_in;   // rows of every page, then its present values (alive until the synchronisation: the upload reads it)
     auto stats_launch = [&]() -> int {
-        if (!want_stats) return PF_OK;
+        if (!run_stats) return PF_OK;
         StatArgs sa{};
         sa.tiles = reinterpret_cast<const StatTile*>(A + o_stt); sa.ptile = reinterpret_cast<const uint32_t*>(A + o_stp);
         sa.n_tiles = uint32_t(stiles.size()); sa.n_pages = uint32_t(pp.size());
@@ -821,9 +840,30 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         HIPCHK(ctx, hipMemcpyAsync(A + o_stp, sptile.data(), 4 * sptile.size(), hipMemcpyHostToDevice, st));
         enc_stats(ea, sa, st);
         HIPCHK(ctx, hipGetLastError());
+        if (want_index) {
+            px_in.resize(2 * n_px);
+            for (size_t i = 0; i < n_px; i++) { px_in[i] = uint32_t(pp[i].r1 - pp[i].r0); px_in[n_px + i] = pp[i].cnt; }
+            HIPCHK(ctx, hipMemcpyAsync(A + o_xin, px_in.data(), 8 * n_px, hipMemcpyHostToDevice, st));
+            PgIndexArgs xa{};
+            xa.pages = sa.out;
+            xa.rows = reinterpret_cast<const uint32_t*>(A + o_xin); xa.cnt = xa.rows + n_px;
+            xa.n_pages = uint32_t(n_px); xa.trunc = px_trunc; xa.value_cap = uint32_t(px_cap);
+            xa.nn = reinterpret_cast<uint32_t*>(A + o_xnn);
+            xa.head = reinterpret_cast<PgIndexHead*>(A + o_xout);
+            xa.null_counts = reinterpret_cast<long long*>(A + o_xout + px_nc);
+            xa.off = reinterpret_cast<uint32_t*>(A + o_xout + px_off);
+            xa.null_pages = A + o_xout + px_np;
+            xa.values = A + o_xout + px_val;
+            enc_pgindex(ea, xa, st);
+            HIPCHK(ctx, hipGetLastError());
+        }
         return PF_OK;
     };
     auto stats_fetch = [&]() -> int {
+        if (want_index) {   // one block, in pinned memory, under the synchronisation the bodies wait for
+            HIPCHK(ctx, ctx->h_enc_px.ensure(px_bytes));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_enc_px.p, A + o_xout, px_bytes, hipMemcpyDeviceToHost, st));
+        }
         if (!want_stats) return PF_OK;
         HIPCHK(ctx, ctx->h_enc_st.ensure(st_bytes));
         uint8_t* h = static_cast<uint8_t*>(ctx->h_enc_st.p);
@@ -1087,6 +1127,9 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         bi = 1;
     }
     out->data_page_offset = int64_t(o.size());
+    ctx->h_enc_pgoff.assign(n_px, 0);
+    ctx->h_enc_pgrow.assign(n_px, 0);
+    ctx->h_enc_pgsize.assign(n_px, 0);
     for (size_t i = 0; i < pp.size(); i++, bi++) {
         const PagePlanE& p = pp[i];
         const int64_t rows = p.r1 - p.r0;
@@ -1121,6 +1164,11 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
         unc += int64_t(o.size() - h0) + h.uncompressed_size;
         o.insert(o.end(), def.begin(), def.end());
         o.insert(o.end(), bodies[bi].begin(), bodies[bi].end());
+        if (want_index) {   // the OffsetIndex entry: the host knows where it put the page
+            ctx->h_enc_pgoff[i] = int64_t(h0);
+            ctx->h_enc_pgsize[i] = int32_t(o.size() - h0);
+            ctx->h_enc_pgrow[i] = p.r0;
+        }
     }
     if (crc_bad) return fail(ctx, PF_ERR_HIP, "encode: the CRC pieces of a page do not add up to its size");
     out->stats_flags = 0;
@@ -1162,6 +1210,28 @@ extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_
     out->bloom_len = int32_t(bloom);
     out->bloom_ms = 0.f;
     if (bloom && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&out->bloom_ms, ctx->ev_bloom[0], ctx->ev_bloom[1]));
+    out->index_pages = 0;
+    out->page_offset = nullptr; out->page_size = nullptr; out->page_first_row = nullptr;
+    out->column_index = 0; out->boundary_order = 0;
+    out->index_null_pages = nullptr; out->index_null_counts = nullptr;
+    out->index_values = nullptr; out->index_value_off = nullptr;
+    if (want_index) {
+        const uint8_t* h = static_cast<const uint8_t*>(ctx->h_enc_px.p);
+        const PgIndexHead* hd = reinterpret_cast<const PgIndexHead*>(h);
+        if (hd->value_bytes > px_cap && hd->valid) return fail(ctx, PF_ERR_HIP, "encode: the page index values exceed their block");
+        out->index_pages = int32_t(n_px);
+        out->page_offset = ctx->h_enc_pgoff.data();
+        out->page_size = ctx->h_enc_pgsize.data();
+        out->page_first_row = ctx->h_enc_pgrow.data();
+        out->column_index = hd->valid ? 1 : 0;
+        out->boundary_order = hd->valid ? int32_t(hd->order) : 0;
+        out->index_null_pages = h + px_np;
+        out->index_null_counts = reinterpret_cast<const int64_t*>(h + px_nc);
+        if (hd->valid) {
+            out->index_values = h + px_val;
+            out->index_value_off = reinterpret_cast<const uint32_t*>(h + px_off);
+        }
+    }
     out->snappy_in = 0;
     out->snappy_out = 0;
     if (compressed)
@@ -1296,6 +1366,7 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_res.release();
     ctx->h_enc_slots.release();
     ctx->h_enc_st.release();
+    ctx->h_enc_px.release();
     ctx->h_enc_bloom.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_bloom) if (e) (void)hipEventDestroy(e);

@@ -107,7 +107,50 @@ struct ChunkRec {
     std::vector<uint8_t> bloom;   // the Bloom filter's bitset, kept until close (empty: none)
     int64_t bloom_offset = -1;    // file offset of its BloomFilterHeader
     int32_t bloom_length = 0;     // header + bitset
+    // page index (pf_encoded_chunk.index_*; has_offset_index false: none), kept until close
+    bool has_offset_index = false, has_column_index = false;
+    std::vector<int64_t> page_offset, page_first_row;   // page_offset: in the file
+    std::vector<int32_t> page_size;
+    int32_t boundary_order = 0;
+    std::vector<uint8_t> null_pages, index_values;
+    std::vector<int64_t> null_counts;
+    std::vector<uint32_t> value_off;
+    int64_t ci_offset = -1, oi_offset = -1;
+    int32_t ci_length = 0, oi_length = 0;
 };
+
+// ColumnIndex (parquet.thrift): 1 null_pages list<bool>, 2 min_values list<binary>, 3 max_values list<binary>,
+// 4 boundary_order, 5 null_counts list<i64>.
+void write_column_index(ThriftWriter& t, const ChunkRec& c) {
+    const size_t n = c.null_pages.size();
+    t.list_header(1, T_TRUE, n);   // list<bool>: element type 1, one byte each (1 true, 2 false)
+    for (size_t i = 0; i < n; i++) t.out.push_back(c.null_pages[i] ? T_TRUE : T_FALSE);
+    for (int k = 0; k < 2; k++) {
+        t.list_header(2 + k, T_BINARY, n);
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t b = c.value_off[2 * i + size_t(k)], e = c.value_off[2 * i + size_t(k) + 1];
+            t.uvarint(e - b);
+            t.out.insert(t.out.end(), c.index_values.begin() + b, c.index_values.begin() + e);
+        }
+    }
+    t.i32(4, c.boundary_order);
+    t.list_header(5, T_I64, n);
+    for (size_t i = 0; i < n; i++) t.zigzag(c.null_counts[i]);
+    t.stop();
+}
+
+// OffsetIndex: 1 page_locations list<PageLocation {1 offset, 2 compressed_page_size, 3 first_row_index}>.
+void write_offset_index(ThriftWriter& t, const ChunkRec& c) {
+    t.list_header(1, T_STRUCT, c.page_offset.size());
+    for (size_t i = 0; i < c.page_offset.size(); i++) {
+        t.list_struct_begin();
+        t.i64(1, c.page_offset[i]);
+        t.i32(2, c.page_size[i]);
+        t.i64(3, c.page_first_row[i]);
+        t.end_struct();
+    }
+    t.stop();
+}
 struct RowGroupRec {
     int64_t num_rows = 0;
     std::vector<ChunkRec> chunks;
@@ -122,7 +165,7 @@ struct pf_writer {
     std::vector<RowGroupRec> groups;
     RowGroupRec cur;
     bool failed = false;
-    bool any_stats = false;   // a chunk carried statistics: the footer declares column_orders
+    bool any_stats = false;   // a chunk carried statistics or a ColumnIndex: the footer declares column_orders
 };
 
 namespace {
@@ -190,9 +233,40 @@ int pf_writer_add_chunk(pf_writer* w, int field, const pf_encoded_chunk* c) {
             return werr(PF_ERR_INVALID_ARG, "chunk Bloom filter: bloom_len must be a power of two >= 32 and bloom not null");
         r.bloom.assign(c->bloom, c->bloom + c->bloom_len);
     }
+    if (c->index_pages < 0) return werr(PF_ERR_INVALID_ARG, "chunk page index: negative index_pages");
+    if (c->index_pages > 0) {
+        const size_t np = size_t(c->index_pages);
+        if (!c->page_offset || !c->page_size || !c->page_first_row || !c->index_null_pages || !c->index_null_counts)
+            return werr(PF_ERR_INVALID_ARG, "chunk page index: index_pages set but an array is missing");
+        if (c->column_index != 0 && c->column_index != 1) return werr(PF_ERR_INVALID_ARG, "chunk page index: column_index must be 0 or 1");
+        if (c->boundary_order < 0 || c->boundary_order > 2) return werr(PF_ERR_INVALID_ARG, "chunk page index: boundary_order must be 0, 1 or 2");
+        for (size_t i = 0; i < np; i++)
+            if (c->page_offset[i] < 0 || c->page_size[i] < 0 || c->page_offset[i] + c->page_size[i] > c->size || c->page_first_row[i] < 0)
+                return werr(PF_ERR_INVALID_ARG, "chunk page index: a page location lies outside the chunk");
+        r.has_offset_index = true;
+        r.page_offset.resize(np);
+        for (size_t i = 0; i < np; i++) r.page_offset[i] = w->pos + c->page_offset[i];
+        r.page_size.assign(c->page_size, c->page_size + np);
+        r.page_first_row.assign(c->page_first_row, c->page_first_row + np);
+        if (c->column_index == 1) {
+            if (!c->index_value_off || (!c->index_values && c->index_value_off[2 * np] > 0))
+                return werr(PF_ERR_INVALID_ARG, "chunk page index: column_index set but the values are missing");
+            for (size_t i = 0; i < 2 * np; i++)
+                if (c->index_value_off[i] > c->index_value_off[i + 1])
+                    return werr(PF_ERR_INVALID_ARG, "chunk page index: value offsets out of order");
+            r.has_column_index = true;
+            r.boundary_order = c->boundary_order;
+            r.null_pages.assign(c->index_null_pages, c->index_null_pages + np);
+            r.null_counts.assign(c->index_null_counts, c->index_null_counts + np);
+            r.value_off.assign(c->index_value_off, c->index_value_off + 2 * np + 1);
+            if (r.value_off[2 * np]) r.index_values.assign(c->index_values, c->index_values + r.value_off[2 * np]);
+        }
+    } else if (c->column_index != 0) {
+        return werr(PF_ERR_INVALID_ARG, "chunk page index: column_index without index_pages");
+    }
     int rc = put(w, c->bytes, size_t(c->size));
     if (rc) return rc;
-    if (r.stats.present) w->any_stats = true;
+    if (r.stats.present || r.has_column_index) w->any_stats = true;
     w->cur.chunks.push_back(r);
     return PF_OK;
 }
@@ -208,14 +282,27 @@ int pf_writer_end_row_group(pf_writer* w, int64_t num_rows) {
     return PF_OK;
 }
 
-// Bloom filters, behind the last row group in row-group then column order (parquet-mr 1.12 ParquetFileWriter.end,
-// pyarrow): BloomFilterHeader { 1 numBytes, 2 algorithm { 1 BLOCK {} }, 3 hash { 1 XXHASH {} }, 4 compression
+// Behind the last row group, in the order of parquet-mr 1.12's ParquetFileWriter.end (pyarrow's too): every
+// ColumnIndex, then every OffsetIndex, then the Bloom filters, each in row-group then column order.
+// BloomFilterHeader { 1 numBytes, 2 algorithm { 1 BLOCK {} }, 3 hash { 1 XXHASH {} }, 4 compression
 // { 1 UNCOMPRESSED {} } }, then the bitset.
 // FileMetaData: 1 version, 2 schema, 3 num_rows, 4 row_groups, 6 created_by, 7 column_orders (only with statistics).
 int pf_writer_close(pf_writer* w) {
     if (!w) return werr(PF_ERR_INVALID_ARG, "null writer");
     int rc = PF_OK;
     if (!w->cur.chunks.empty()) rc = werr(PF_ERR_STATE, "unfinished row group");
+    for (int pass = 0; pass < 2; pass++)   // 0: the ColumnIndexes, 1: the OffsetIndexes
+        for (RowGroupRec& g : w->groups)
+            for (ChunkRec& c : g.chunks) {
+                if (!(pass == 0 ? c.has_column_index : c.has_offset_index) || rc != PF_OK || w->failed) continue;
+                std::vector<uint8_t> h;
+                ThriftWriter t(h);
+                if (pass == 0) write_column_index(t, c);
+                else write_offset_index(t, c);
+                (pass == 0 ? c.ci_offset : c.oi_offset) = w->pos;
+                (pass == 0 ? c.ci_length : c.oi_length) = int32_t(h.size());
+                rc = put(w, h.data(), h.size());
+            }
     for (RowGroupRec& g : w->groups)
         for (ChunkRec& c : g.chunks) {
             if (c.bloom.empty() || rc != PF_OK || w->failed) continue;
@@ -300,6 +387,8 @@ int pf_writer_close(pf_writer* w) {
                     t.i32(15, c.bloom_length);
                 }
                 t.end_struct();
+                if (c.oi_offset >= 0) { t.i64(4, c.oi_offset); t.i32(5, c.oi_length); }
+                if (c.ci_offset >= 0) { t.i64(6, c.ci_offset); t.i32(7, c.ci_length); }
                 t.end_struct();
             }
             t.i64(2, total_unc);

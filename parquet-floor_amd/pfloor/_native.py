@@ -73,6 +73,16 @@ class ScanResult(C.Structure):
     _fields_ = [("n_pages", C.c_int32), ("status", C.c_int32), ("err_page", C.c_int32), ("crc_pages", C.c_int32)]
 
 
+class PageLocation(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("compressed_page_size", C.c_int32), ("first_row_index", C.c_int64)]
+
+
+class ColumnIndex(C.Structure):
+    _fields_ = [("n_pages", C.c_int32), ("boundary_order", C.c_int32), ("null_pages", C.POINTER(C.c_uint8)),
+                ("null_counts", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_uint8)),
+                ("value_off", C.POINTER(C.c_uint32))]
+
+
 class PfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -152,6 +162,9 @@ def _load(path):
         "pf_file_chunk_desc": ([vp, i32, i32, C.c_uint64, C.POINTER(ChunkDesc)], C.c_int),
         "pf_file_read": ([vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "pf_file_chunk_bloom": ([vp, i32, i32, i64p, C.POINTER(C.c_int32)], C.c_int),
+        "pf_file_chunk_index_ranges": ([vp, i32, i32, i64p, C.POINTER(C.c_int32), i64p, C.POINTER(C.c_int32)], C.c_int),
+        "pf_file_offset_index": ([vp, i32, i32, C.POINTER(PageLocation), i32, C.POINTER(C.c_int)], C.c_int),
+        "pf_file_column_index": ([vp, i32, i32, C.POINTER(ColumnIndex)], C.c_int),
         "pf_xxh64": ([vp, sz, C.c_uint64], C.c_uint64),
         "pf_bloom_check": ([vp, sz, C.c_uint64], C.c_int),
         "pf_file_created_by": ([vp], C.c_char_p),

@@ -7,7 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import ChunkDesc, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, ScanChunk, ScanResult, check, lib
+from ._native import (ChunkDesc, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, PageLocation, ScanChunk,
+                      ScanResult, check, lib)
 
 CONVERTED_UTF8, CONVERTED_ENUM, CONVERTED_JSON = 0, 4, 19
 LOGICAL_STRING, LOGICAL_ENUM, LOGICAL_JSON = 1, 4, 12
@@ -95,6 +96,43 @@ class ParquetFile:
         d = ChunkDesc()
         check(lib().pf_file_chunk_desc(self.h, rg, col, offset_in_buffer, C.byref(d)), None, f"pages rg{rg} c{col}")
         return d
+
+    def index_ranges(self, rg, col):
+        """((column_index_offset, length) or None, (offset_index_offset, length) or None) of a chunk."""
+        co, oo, cl, ol = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().pf_file_chunk_index_ranges(self.h, rg, col, C.byref(co), C.byref(cl), C.byref(oo), C.byref(ol)),
+              None, f"index ranges rg{rg} c{col}")
+        return ((co.value, cl.value) if co.value >= 0 else None, (oo.value, ol.value) if oo.value >= 0 else None)
+
+    def page_index(self, rg, col):
+        """The chunk's page index as the file holds it: {"offset_index": [(offset, compressed_page_size,
+        first_row_index)] or None, "column_index": {"null_pages": [bool], "min_values": [bytes], "max_values":
+        [bytes], "boundary_order": 0 UNORDERED | 1 ASCENDING | 2 DESCENDING, "null_counts": [int] or None} or None}
+        (pf_file_offset_index, pf_file_column_index; values are PLAIN bytes, possibly truncated bounds)."""
+        ci_range, oi_range = self.index_ranges(rg, col)
+        out = {"offset_index": None, "column_index": None}
+        if oi_range:
+            n = C.c_int()
+            rc = lib().pf_file_offset_index(self.h, rg, col, None, 0, C.byref(n))
+            if rc != -6:   # PF_ERR_CAPACITY reports the count
+                check(rc, None, f"offset index rg{rg} c{col}")
+            locs = (PageLocation * max(1, n.value))()
+            check(lib().pf_file_offset_index(self.h, rg, col, locs, n.value, C.byref(n)), None, f"offset index rg{rg} c{col}")
+            out["offset_index"] = [(locs[i].offset, locs[i].compressed_page_size, locs[i].first_row_index)
+                                   for i in range(n.value)]
+        if ci_range:
+            ci = ColumnIndex()
+            check(lib().pf_file_column_index(self.h, rg, col, C.byref(ci)), None, f"column index rg{rg} c{col}")
+            n = ci.n_pages
+            off = [ci.value_off[i] for i in range(2 * n + 1)]
+            raw = C.string_at(ci.values, off[-1])
+            out["column_index"] = {
+                "null_pages": [bool(ci.null_pages[i]) for i in range(n)],
+                "min_values": [raw[off[2 * i]:off[2 * i + 1]] for i in range(n)],
+                "max_values": [raw[off[2 * i + 1]:off[2 * i + 2]] for i in range(n)],
+                "boundary_order": ci.boundary_order,
+                "null_counts": [ci.null_counts[i] for i in range(n)] if ci.null_counts else None}
+        return out
 
     def read_into(self, offset, size, dst_ptr):
         check(lib().pf_file_read(self.h, offset, size, C.c_void_p(dst_ptr)))

@@ -45,7 +45,17 @@ The filter does not depend on how the chunk is encoded. BOOLEAN columns get none
 Differences that are allowed by the format and documented in DESIGN.md: the fallback is decided
 for the whole chunk (parquet-mr switches mid-chunk and also drops a dictionary that does not
 compress, isCompressionSatisfying), ids are written as one bit-packed run per page unless
-hybrid_runs is set, statistics, page checksums and Bloom filters are opt-in, no column index / offset index is written.
+hybrid_runs is set, statistics, page checksums, Bloom filters and the page index are opt-in.
+
+With page_index=True (PF_ENCODE_PAGE_INDEX) every chunk gets a ColumnIndex (per data page: null_page, min, max,
+null_count, and the boundary order of the pages) and an OffsetIndex (every data page's file offset, size and first
+row), the structures parquet-mr's ColumnIndexFilter, Impala, Trino, Spark and DuckDB skip pages by. The lists are
+built on the GPU from the page results of the statistics kernels (k_enc_pgindex) and stored between the last row
+group and the Bloom filters, all ColumnIndexes before all OffsetIndexes, as parquet-mr 1.12 and pyarrow store them.
+BYTE_ARRAY min and max are truncated to index_truncate bytes (0: 64, parquet-mr's
+parquet.columnindex.truncate.length; -1: never) under the unsigned bytewise order; UTF-8 is not kept valid, which only
+non-ASCII strings can notice. A chunk with a page of NaNs alone, or with a max that cannot be shortened, gets an
+OffsetIndex only. The option is independent of statistics=True.
 """
 import ctypes as C
 import math
@@ -58,7 +68,8 @@ from ._native import PfError, check, lib
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BINARY, FIXED_LEN_BYTE_ARRAY = 0, 1, 2, 3, 4, 5, 6, 7
 UNCOMPRESSED, SNAPPY, ZSTD = 0, 1, 6   # pf_encode_column.codec (PF_CODEC_*): the codecs the write path has
 ENCODE_DICTIONARY, ENCODE_DELTA_FALLBACK, ENCODE_HYBRID_RUNS = 1, 2, 4   # pf_encode_column.dictionary bits (PF_ENCODE_*)
-ENCODE_STATISTICS, ENCODE_PAGE_CRC = 8, 16
+ENCODE_STATISTICS, ENCODE_PAGE_CRC, ENCODE_PAGE_INDEX = 8, 16, 32
+UNORDERED, ASCENDING, DESCENDING = 0, 1, 2   # pf_encoded_chunk.boundary_order
 STATS_NULL_COUNT, STATS_MIN_MAX = 1, 2   # pf_encoded_chunk.stats_flags (PF_STATS_*)
 BLOOM_MIN_BYTES, BLOOM_MAX_BYTES = 32, 128 << 20   # pf_encode_column.bloom_bytes: a power of two between them
 _WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, FLOAT: 4, DOUBLE: 8}
@@ -71,7 +82,8 @@ class EncodeColumn(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("max_def", C.c_int32), ("num_rows", C.c_int64),
                 ("values", C.c_void_p), ("validity", C.c_void_p), ("offsets", C.c_void_p), ("chars", C.c_void_p),
                 ("chars_len", C.c_int64), ("dictionary", C.c_int32), ("page_rows", C.c_int32),
-                ("dict_page_limit", C.c_int32), ("codec", C.c_int32), ("bloom_bytes", C.c_int32)]
+                ("dict_page_limit", C.c_int32), ("codec", C.c_int32), ("bloom_bytes", C.c_int32),
+                ("index_truncate", C.c_int32)]
 
 
 class EncodedChunk(C.Structure):
@@ -82,7 +94,32 @@ class EncodedChunk(C.Structure):
                 ("snappy_in", C.c_int64), ("snappy_out", C.c_int64),
                 ("stats_flags", C.c_int32), ("stat_min_len", C.c_int32), ("stat_max_len", C.c_int32),
                 ("null_count", C.c_int64), ("stat_min", C.c_void_p), ("stat_max", C.c_void_p),
-                ("bloom", C.c_void_p), ("bloom_len", C.c_int32), ("bloom_ms", C.c_float)]
+                ("bloom", C.c_void_p), ("bloom_len", C.c_int32), ("bloom_ms", C.c_float),
+                ("index_pages", C.c_int32), ("page_offset", C.POINTER(C.c_int64)), ("page_size", C.POINTER(C.c_int32)),
+                ("page_first_row", C.POINTER(C.c_int64)), ("column_index", C.c_int32), ("boundary_order", C.c_int32),
+                ("index_null_pages", C.POINTER(C.c_uint8)), ("index_null_counts", C.POINTER(C.c_int64)),
+                ("index_values", C.POINTER(C.c_uint8)), ("index_value_off", C.POINTER(C.c_uint32))]
+
+    def page_locations(self):
+        """[(offset relative to bytes, size, first row)] of the data pages (PF_ENCODE_PAGE_INDEX), or None."""
+        n = self.index_pages
+        if n <= 0:
+            return None
+        return [(self.page_offset[i], self.page_size[i], self.page_first_row[i]) for i in range(n)]
+
+    def page_column_index(self):
+        """{"null_pages", "min_values", "max_values", "boundary_order", "null_counts"} of the chunk's ColumnIndex, or
+        None when it has none (column_index == 0)."""
+        n = self.index_pages
+        if n <= 0 or not self.column_index:
+            return None
+        off = [self.index_value_off[i] for i in range(2 * n + 1)]
+        raw = C.string_at(self.index_values, off[-1]) if off[-1] else b""
+        return {"null_pages": [bool(self.index_null_pages[i]) for i in range(n)],
+                "min_values": [raw[off[2 * i]:off[2 * i + 1]] for i in range(n)],
+                "max_values": [raw[off[2 * i + 1]:off[2 * i + 2]] for i in range(n)],
+                "boundary_order": self.boundary_order,
+                "null_counts": [self.index_null_counts[i] for i in range(n)]}
 
     def statistics(self):
         """(null_count or None, min bytes or None, max bytes or None) of the chunk."""
@@ -248,8 +285,12 @@ class GpuColumnEncoder:
         self.dec = decoder
 
     def encode(self, field, data, validity, n, dictionary=True, page_rows=0, dict_page_limit=0, codec=1,
-               delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False, bloom_bytes=0):
-        """bloom_bytes: the chunk's split-block Bloom filter, a power of two in [32, 128 MiB] (0: none;
+               delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False, bloom_bytes=0,
+               page_index=False, index_truncate=0):
+        """page_index: PF_ENCODE_PAGE_INDEX, the chunk's ColumnIndex lists and page locations
+        (EncodedChunk.page_column_index(), page_locations()); index_truncate: the longest BINARY min / max in it (0: 64,
+        -1: no truncation, else 1 .. 2047).
+        bloom_bytes: the chunk's split-block Bloom filter, a power of two in [32, 128 MiB] (0: none;
         EncodedChunk.bloom_filter()). delta_fallback: PF_ENCODE_DELTA_FALLBACK, DELTA_* data pages for a chunk that is not
         dictionary-encoded (INT32, INT64, BINARY). hybrid_runs: PF_ENCODE_HYBRID_RUNS, ids, definition
         levels and BOOLEAN values as parquet-mr's hybrid encoder writes them (RLE runs and bit-packed groups).
@@ -280,7 +321,8 @@ class GpuColumnEncoder:
             c.validity = v.ctypes.data
         c.dictionary = ((ENCODE_DICTIONARY if dictionary else 0) | (ENCODE_DELTA_FALLBACK if delta_fallback else 0) |
                         (ENCODE_HYBRID_RUNS if hybrid_runs else 0) | (ENCODE_STATISTICS if statistics else 0) |
-                        (ENCODE_PAGE_CRC if page_checksums else 0))
+                        (ENCODE_PAGE_CRC if page_checksums else 0) | (ENCODE_PAGE_INDEX if page_index else 0))
+        c.index_truncate = index_truncate
         c.page_rows = page_rows
         c.dict_page_limit = dict_page_limit
         c.codec = codec
@@ -297,8 +339,12 @@ class ParquetWriter:
 
     def __init__(self, schema, path, dehydrator, row_group_rows=1 << 20, device=0, decoder=None, codec=SNAPPY,
                  decoders=None, delta_fallback=False, hybrid_runs=False, statistics=False, page_checksums=False,
-                 bloom_filters=None, bloom_fpp=0.01, bloom_max_bytes=1 << 20):
-        """bloom_filters: {field name: expected distinct count | True (bloom_max_bytes) | {"bytes": n}}, the columns
+                 bloom_filters=None, bloom_fpp=0.01, bloom_max_bytes=1 << 20, page_index=False, index_truncate=0,
+                 page_rows=0):
+        """page_rows: rows per data page (0: 20,000, parquet-mr's page.row.count.limit; rounded up to a multiple of 8).
+        page_index: a ColumnIndex and an OffsetIndex for every chunk (see above); index_truncate: the longest BINARY
+        min / max in a ColumnIndex (0: 64, -1: no truncation, else 1 .. 2047).
+        bloom_filters: {field name: expected distinct count | True (bloom_max_bytes) | {"bytes": n}}, the columns
         that get a Bloom filter, sized by bloom_optimal_bytes(ndv, bloom_fpp, bloom_max_bytes) (see above); an unknown
         name is a ValueError, a BOOLEAN field gets none.
         codec: SNAPPY (the default), ZSTD or UNCOMPRESSED; any other is refused (PF_ERR_UNSUPPORTED_CODEC).
@@ -322,6 +368,9 @@ class ParquetWriter:
         self.hybrid_runs = hybrid_runs
         self.statistics = statistics
         self.page_checksums = page_checksums
+        self.page_index = page_index
+        self.index_truncate = index_truncate
+        self.page_rows = page_rows
         self.buf = _RowBuffer(schema)
         self.last_chunks = []     # (dict_entries, data_encoding, fallback) of the last row group
         fields = (WriteField * len(schema.fields))()
@@ -407,7 +456,8 @@ class ParquetWriter:
                     f, d, validity = work[i]
                     out = enc.encode(f, d, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
                                      hybrid_runs=self.hybrid_runs, statistics=self.statistics,
-                                     page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i])
+                                     page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i],
+                                     page_index=self.page_index, index_truncate=self.index_truncate, page_rows=self.page_rows)
                     keep = C.create_string_buffer(C.string_at(out.bytes, out.size), max(1, out.size))
                     cp = EncodedChunk.from_buffer_copy(out)
                     cp.bytes = C.cast(keep, C.c_void_p)
@@ -420,6 +470,21 @@ class ParquetWriter:
                         hi = C.create_string_buffer(C.string_at(out.stat_max, out.stat_max_len), max(1, out.stat_max_len))
                         cp.stat_min, cp.stat_max = C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p)
                         keep = (keep, lo, hi)
+                    if out.index_pages > 0:   # ... and the page index
+                        held = [keep]
+                        np_, nv = out.index_pages, (out.index_value_off[2 * out.index_pages] if out.column_index else 0)
+                        for name, ct, cnt in (("page_offset", C.c_int64, np_), ("page_size", C.c_int32, np_),
+                                              ("page_first_row", C.c_int64, np_), ("index_null_pages", C.c_uint8, np_),
+                                              ("index_null_counts", C.c_int64, np_), ("index_values", C.c_uint8, nv),
+                                              ("index_value_off", C.c_uint32, 2 * np_ + 1)):
+                            src = getattr(out, name)
+                            if not src:
+                                continue
+                            arr = (ct * max(1, cnt))()
+                            C.memmove(arr, src, C.sizeof(ct) * cnt)
+                            setattr(cp, name, C.cast(arr, C.POINTER(ct)))
+                            held.append(arr)
+                        keep = tuple(held)
                     results[i] = (cp, keep)
             except Exception as e:   # reported after the join
                 errs.append(e)
@@ -445,7 +510,8 @@ class ParquetWriter:
     def _encode_add(self, f, data, validity, n, i):
         out = self.enc.encode(f, data, validity, n, codec=self.codec, delta_fallback=self.delta_fallback,
                               hybrid_runs=self.hybrid_runs, statistics=self.statistics,
-                              page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i])
+                              page_checksums=self.page_checksums, bloom_bytes=self.bloom_bytes[i],
+                              page_index=self.page_index, index_truncate=self.index_truncate, page_rows=self.page_rows)
         self._add(out, i)
         return out
 
