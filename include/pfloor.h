@@ -241,7 +241,14 @@ int pf_snappy_last_fallback(pf_ctx* ctx);
  *      (parquet-mr ParquetReadOptions.usePageChecksumVerification: a page whose PageHeader.crc,
  *      field 4, differs from the CRC32 of its on-disk page bytes is rejected). Pages are read
  *      until the chunk's num_values level entries have been seen; INDEX / unknown pages are
- *      skipped; the descriptors are exactly what pf_file_chunk_desc (the host walk) produces. */
+ *      skipped; the descriptors are exactly what pf_file_chunk_desc (the host walk) produces.
+ *      Both walks read Thrift compact as libthrift does: a field id is kept as i16, a bool inside a
+ *      list, set or map is one byte, a varint has at most 10 bytes. A value they skip (an unknown
+ *      field, Statistics min / max, ...) may have at most PF_THRIFT_MAX_NESTING containers (struct,
+ *      list, set, map; the value itself included) open at once; one more is PF_ERR_CORRUPT_PAGE
+ *      (libthrift itself reads deeper ones; no writer emits them). The walk of a chunk takes a number of steps bounded by the
+ *      chunk's size, whatever its bytes say. */
+#define PF_THRIFT_MAX_NESTING 16
 typedef struct pf_scan_chunk {
     uint64_t chunk_offset;        /* first byte of the chunk in `bytes` */
     uint64_t chunk_size;          /* ColumnMetaData.total_compressed_size */
@@ -257,7 +264,9 @@ typedef struct pf_scan_result {
 } pf_scan_result;
 /* Synchronous. `bytes` is host memory (copied to the device) unless bytes_on_device != 0.
  * pages_out has room for every chunk's [page_base, page_base + page_cap) slots; results has
- * n_chunks entries. Returns the first chunk error (PF_OK if none). */
+ * n_chunks entries. Returns the first chunk error (PF_OK if none). Of a chunk's slots only the
+ * first n_pages are written with descriptors: the slots past them, and slots no chunk owns, hold
+ * whatever the context's scan buffer held before (unspecified). */
 int pf_scan_pages(pf_ctx* ctx, const pf_scan_chunk* chunks, int n_chunks, const uint8_t* bytes, size_t n_bytes,
                   int bytes_on_device, int verify_crc, pf_page_desc* pages_out, pf_scan_result* results);
 /* ---- host-side metadata parse: the stand-in for the Java side's parquet-mr footer /
@@ -284,7 +293,8 @@ int pf_file_row_group_rows(pf_file* f, int row_group, int64_t* out);
 /* Byte range [start, start+size) of a chunk in the file. */
 int pf_file_chunk_range(pf_file* f, int row_group, int column, uint64_t* start, uint64_t* size);
 /* Parse the chunk's page headers; fills *desc (pages owned by the pf_file) with
- * chunk_offset = `chunk_offset_in_buffer`. */
+ * chunk_offset = `chunk_offset_in_buffer`. The walk pf_scan_pages mirrors: the same Thrift reading
+ * and the same PF_THRIFT_MAX_NESTING (above). */
 int pf_file_chunk_desc(pf_file* f, int row_group, int column, uint64_t chunk_offset_in_buffer,
                        pf_chunk_desc* desc);
 /* Read raw bytes of the file (host). */

@@ -48,75 +48,75 @@ static int buf_put(buf_t* b, const void* src, size_t n) {
 }
 
 /* ------------------------------------------------------------------ Thrift compact protocol */
-typedef struct { const uint8_t* p; const uint8_t* end; int err; } tr_t;
+typedef struct { const uint8_t* p; const uint8_t* end; int err; int max_nest; } tr_t;   /* max_nest 0: 64 (the footer) */
 
 static uint8_t tr_byte(tr_t* r) { if (r->p >= r->end) { r->err = 1; return 0; } return *r->p++; }
-static uint64_t tr_varint(tr_t* r) {
-    uint64_t v = 0; int sh = 0;
-    for (;;) {
+static uint64_t tr_varint(tr_t* r) {   /* at most 10 bytes */
+    uint64_t v = 0;
+    for (int sh = 0; sh < 70; sh += 7) {
         uint8_t c = tr_byte(r);
         if (r->err) return 0;
         if (sh < 64) v |= (uint64_t)(c & 0x7f) << sh;
         if (!(c & 0x80)) return v;
-        sh += 7;
-        if (sh > 70) { r->err = 1; return 0; }
     }
+    r->err = 1;
+    return 0;
 }
 static int64_t tr_zz(tr_t* r) { uint64_t v = tr_varint(r); return (int64_t)(v >> 1) ^ -(int64_t)(v & 1); }
 
-static void tr_skip(tr_t* r, int type, int depth);
-static void tr_skip_struct(tr_t* r, int depth) {
-    if (depth > 64) { r->err = 1; return; }
-    for (;;) {
-        uint8_t h = tr_byte(r);
-        if (r->err || h == 0) return;
-        if ((h >> 4) == 0) tr_zz(r);
-        tr_skip(r, h & 0xf, depth + 1);
-        if (r->err) return;
-    }
-}
-static void tr_skip(tr_t* r, int type, int depth) {
+/* Skip a value with `open` containers around it; inside: an element of a list, set or map, where a bool is
+ * one byte. Every step consumes a byte or closes a container, so a skip ends within the bytes that remain
+ * whatever the counts say. A value may have at most max_nest containers open at once. */
+static void tr_skip_in(tr_t* r, int type, int open, int inside) {
     switch (type) {
-    case 1: case 2: return;                       /* bool in field header */
+    case 1: case 2: if (inside) tr_byte(r); return;   /* as a struct field: in the field header */
     case 3: tr_byte(r); return;
     case 4: case 5: case 6: tr_varint(r); return;
     case 7: if (r->end - r->p < 8) r->err = 1; else r->p += 8; return;
-    case 8: { uint64_t n = tr_varint(r); if ((uint64_t)(r->end - r->p) < n) r->err = 1; else r->p += n; return; }
-    case 9: case 10: {
-        uint8_t h = tr_byte(r); uint64_t n = h >> 4; int et = h & 0xf;
-        if (n == 15) n = tr_varint(r);
-        for (uint64_t i = 0; i < n && !r->err; i++) {
-            if (et == 1 || et == 2) tr_byte(r); else tr_skip(r, et, depth + 1);
-        }
-        return;
-    }
-    case 11: {
-        uint64_t n = tr_varint(r);
-        if (n == 0) return;
-        uint8_t kv = tr_byte(r);
-        for (uint64_t i = 0; i < n && !r->err; i++) { tr_skip(r, kv >> 4, depth + 1); tr_skip(r, kv & 0xf, depth + 1); }
-        return;
-    }
-    case 12: tr_skip_struct(r, depth + 1); return;
+    case 8: { uint64_t n = tr_varint(r); if (r->err || (uint64_t)(r->end - r->p) < n) r->err = 1; else r->p += n; return; }
+    case 9: case 10: case 11: case 12: break;
     default: r->err = 1; return;
     }
+    if (open >= (r->max_nest ? r->max_nest : 64)) { r->err = 1; return; }
+    if (type == 12) {
+        for (;;) {
+            uint8_t h = tr_byte(r);
+            if (r->err || h == 0) return;
+            if ((h >> 4) == 0) tr_zz(r);
+            tr_skip_in(r, h & 0xf, open + 1, 0);
+            if (r->err) return;
+        }
+    } else if (type == 11) {
+        uint64_t n = tr_varint(r);
+        if (r->err || n == 0) return;
+        uint8_t kv = tr_byte(r);
+        for (uint64_t i = 0; i < n && !r->err; i++) { tr_skip_in(r, kv >> 4, open + 1, 1); if (!r->err) tr_skip_in(r, kv & 0xf, open + 1, 1); }
+    } else {
+        uint8_t h = tr_byte(r); uint64_t n = h >> 4; int et = h & 0xf;
+        if (n == 15) n = tr_varint(r);
+        for (uint64_t i = 0; i < n && !r->err; i++) tr_skip_in(r, et, open + 1, 1);
+    }
 }
-/* iterate fields: returns field id, sets *type; 0 on STOP */
+static void tr_skip(tr_t* r, int type, int depth) { tr_skip_in(r, type, depth, 0); }
+/* iterate fields: returns the field id, sets *type; 0 on STOP. The id is kept as i16, as libthrift's readI16
+ * does; a field whose id is 0 is not a STOP and comes back as TR_ID0, which no caller knows, so it is skipped. */
+#define TR_ID0 0x10000
 static int tr_field(tr_t* r, int* last, int* type) {
     uint8_t h = tr_byte(r);
     if (r->err || h == 0) return 0;
     int d = h >> 4;
     *type = h & 0xf;
-    int id = d ? *last + d : (int)tr_zz(r);
+    int id = d ? *last + d : (int)(int16_t)tr_zz(r);
+    if (r->err) return 0;
     *last = id;
-    return id;
+    return id ? id : TR_ID0;
 }
 static int64_t tr_int(tr_t* r, int type) {
     if (type == 3) return (int8_t)tr_byte(r);
     if (type == 4 || type == 5 || type == 6) return tr_zz(r);
     tr_skip(r, type, 0); r->err = 1; return 0;
 }
-static int tr_bool(tr_t* r, int type) { if (type == 1) return 1; if (type == 2) return 0; tr_skip(r, type, 0); return 0; }
+static int tr_bool(tr_t* r, int type) { if (type == 1) return 1; if (type == 2) return 0; r->err = 1; return 0; }
 static char* tr_string(tr_t* r, int type) {
     if (type != 8) { tr_skip(r, type, 0); return NULL; }
     uint64_t n = tr_varint(r);
@@ -230,7 +230,7 @@ static int parse_row_group(tr_t* r, row_group* g) {
 }
 
 static int parse_footer(pfo_file* f, const uint8_t* p, size_t n) {
-    tr_t r = { p, p + n, 0 };
+    tr_t r = { p, p + n, 0, 0 };
     int last = 0, t, id;
     while ((id = tr_field(&r, &last, &t))) {
         if (id == 2 && t == 9) {
@@ -609,6 +609,7 @@ static int delta_binary_decode(const uint8_t* p, size_t n, int is64, uint64_t* o
 }
 
 /* ------------------------------------------------------------------ page walk */
+#define PAGE_MAX_NEST 16   /* PF_THRIFT_MAX_NESTING (include/pfloor.h): the page walks' limit on a skipped value */
 typedef struct {
     int type; int32_t usize, csize;
     int32_t num_values, encoding, def_enc, rep_enc, num_nulls, num_rows, def_bytes, rep_bytes, is_compressed;
@@ -632,6 +633,13 @@ static int parse_page_header(tr_t* r, page_t* pg) {
                     else if (f2 == 2) pg->encoding = (int32_t)tr_int(r, t2);
                     else if (f2 == 3) pg->def_enc = (int32_t)tr_int(r, t2);
                     else if (f2 == 4) pg->rep_enc = (int32_t)tr_int(r, t2);
+                    else if (f2 == 5 && t2 == 12) {   /* Statistics: walked field by field, as the host walk does */
+                        int l3 = 0, t3, f3;
+                        while ((f3 = tr_field(r, &l3, &t3))) {
+                            if (f3 == 3) (void)tr_int(r, t3); else tr_skip(r, t3, 0);
+                            if (r->err) return -1;
+                        }
+                    }
                     else tr_skip(r, t2, 0);
                 } else if (id == 7) {
                     if (f2 == 1) pg->num_values = (int32_t)tr_int(r, t2);
@@ -939,7 +947,7 @@ int pfo_decode(pfo_file* f, int rg, int col, pfo_column* out) {
         buf_t scratch; memset(&scratch, 0, sizeof scratch);
         /* parquet-mr Chunk.readAllPages: read pages until num_values level entries are seen */
         while (seen < m->num_values && !rc) {
-            tr_t r = { p, e, 0 };
+            tr_t r = { p, e, 0, PAGE_MAX_NEST };
             page_t pg;
             if (parse_page_header(&r, &pg) || pg.csize < 0 || pg.usize < 0 || (int64_t)(e - r.p) < pg.csize) { rc = E_CORRUPT; snprintf(out->error, sizeof out->error, "corrupt page header"); break; }
             const uint8_t* body = r.p;
@@ -1043,7 +1051,7 @@ int pfo_chunk_pages(pfo_file* f, int rg, int col, pfo_page* out, int cap, int ve
     int n = 0;
     while (seen < m->num_values) {
         if (p >= e) { *err_page = n; return E_CORRUPT; }
-        tr_t r = { p, e, 0 };
+        tr_t r = { p, e, 0, PAGE_MAX_NEST };
         page_t pg;
         if (parse_page_header(&r, &pg) || pg.csize < 0 || (int64_t)(e - r.p) < pg.csize) { *err_page = n; return E_CORRUPT; }
         p = r.p + pg.csize;
@@ -1051,6 +1059,11 @@ int pfo_chunk_pages(pfo_file* f, int rg, int col, pfo_page* out, int cap, int ve
         if (pg.type == 2 && n > 0) { *err_page = n; return E_CORRUPT; }
         if (pg.type != 2) {
             if (pg.num_values < 0) { *err_page = n; return E_CORRUPT; }
+            if (pg.type == 3 && (pg.def_bytes < 0 || pg.rep_bytes < 0 ||
+                                 (uint64_t)pg.def_bytes + (uint64_t)pg.rep_bytes > (uint32_t)pg.csize ||
+                                 (uint64_t)pg.def_bytes + (uint64_t)pg.rep_bytes > (uint32_t)pg.usize)) {
+                *err_page = n; return E_CORRUPT;   /* v2 level lengths exceed the page */
+            }
             seen += pg.num_values;
         }
         if (n >= cap) { *err_page = n; return E_CAP; }

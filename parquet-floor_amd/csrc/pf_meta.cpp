@@ -26,6 +26,7 @@ namespace {
 struct ThriftReader {
     const uint8_t* p;
     const uint8_t* end;
+    int max_nest = 64;   // containers a skipped value may have open at once (the page walk: PF_THRIFT_MAX_NESTING)
 
     [[noreturn]] static void fail(const char* what) { throw MetaError(what); }
     uint8_t byte() { if (p >= end) fail("truncated thrift"); return *p++; }
@@ -45,7 +46,7 @@ struct ThriftReader {
         if (h == 0) return false;
         type = h & 0xf;
         int d = h >> 4;
-        id = d ? last + d : int(zigzag());
+        id = d ? last + d : int(int16_t(zigzag()));   // libthrift readI16: (short) zigzagToInt(readVarint32())
         last = id;
         return true;
     }
@@ -74,32 +75,33 @@ struct ThriftReader {
         if (n == 15) n = uvarint();
         return n;
     }
-    void skip(int type, int depth = 0) {
-        if (depth > 64) fail("thrift nesting too deep");
+    // Skip a value of type `type` with `open` containers around it (inside: it is an element of a list, set or
+    // map, where a bool is one byte; as a struct field it is in the field header). Every step either consumes
+    // a byte or closes a container: an element of any type costs at least one byte (an empty struct its STOP,
+    // an empty list or map its header), and a binary's length is checked against the bytes that remain. So a
+    // skip ends within a number of steps bounded by the bytes left, whatever the counts say.
+    void skip(int type, int open = 0, bool inside = false) {
         switch (type) {
-        case 1: case 2: return;
+        case 1: case 2: if (inside) byte(); return;
         case 3: byte(); return;
         case 4: case 5: case 6: uvarint(); return;
         case 7: if (end - p < 8) fail("truncated double"); p += 8; return;
         case 8: { uint64_t n = uvarint(); if (uint64_t(end - p) < n) fail("truncated binary"); p += n; return; }
-        case 9: case 10: {
-            int et; uint64_t n = list(et);
-            for (uint64_t i = 0; i < n; i++) { if (et == 1 || et == 2) byte(); else skip(et, depth + 1); }
-            return;
+        case 9: case 10: case 11: case 12: break;
+        default: fail("bad thrift type");
         }
-        case 11: {
+        if (open >= max_nest) fail("thrift nesting too deep");
+        if (type == 12) {
+            int last = 0, id, t;
+            while (field(last, id, t)) skip(t, open + 1);
+        } else if (type == 11) {
             uint64_t n = uvarint();
             if (!n) return;
             uint8_t kv = byte();
-            for (uint64_t i = 0; i < n; i++) { skip(kv >> 4, depth + 1); skip(kv & 0xf, depth + 1); }
-            return;
-        }
-        case 12: {
-            int last = 0, id, t;
-            while (field(last, id, t)) skip(t, depth + 1);
-            return;
-        }
-        default: fail("bad thrift type");
+            for (uint64_t i = 0; i < n; i++) { skip(kv >> 4, open + 1, true); skip(kv & 0xf, open + 1, true); }
+        } else {
+            int et; uint64_t n = list(et);
+            for (uint64_t i = 0; i < n; i++) skip(et, open + 1, true);
         }
     }
 };
@@ -351,7 +353,7 @@ void FileMeta::walk_pages(const uint8_t* chunk, size_t size, const ChunkMeta& m,
     size_t off = 0;
     bool have_dict = false;
     while (seen < m.num_values) {
-        ThriftReader r{chunk + off, chunk + size};
+        ThriftReader r{chunk + off, chunk + size, PF_THRIFT_MAX_NESTING};
         pf_page_desc d{};
         d.is_compressed = 1;
         d.num_nulls = -1;   // v1 without page statistics: unknown

@@ -30,7 +30,7 @@ namespace pf {
 
 constexpr uint32_t SCAN_STG = 512;     // staged header bytes
 constexpr uint32_t SCAN_MARGIN = 16;   // restage when fewer staged bytes remain ahead (a varint is <= 10)
-constexpr int SKIP_DEPTH = 16;
+constexpr int SKIP_DEPTH = PF_THRIFT_MAX_NESTING;   // containers a skipped value may have open at once (pfloor.h)
 
 struct ThriftDev {
     uint8_t* stg;             // LDS
@@ -71,14 +71,15 @@ struct ThriftDev {
         return 0;
     }
     __device__ int64_t zigzag() { const uint64_t u = uvarint(); return int64_t(u >> 1) ^ -int64_t(u & 1); }
-    // Field header: returns the field id (0 = stop); type in t.
-    __device__ int field(int& last, int& t) {
+    // Field header: false at STOP (or on an error); the type in t, the id in id and last. A long-form id is kept
+    // as i16, as libthrift's readI16 does ((short) zigzagToInt(readVarint32())); an id of 0 is a field like any other.
+    __device__ bool field(int& last, int& t, int& id) {
         const uint32_t b = byte();
-        if (err || b == 0) return 0;
+        if (err || b == 0) return false;
         t = int(b & 0xf);
         const int d = int(b >> 4);
-        last = d ? last + d : int(int16_t(zigzag()));
-        return last;
+        id = last = d ? last + d : int(int16_t(zigzag()));
+        return !err;
     }
     __device__ int64_t integer(int t) {
         if (t == 3) return int64_t(int8_t(byte()));
@@ -91,55 +92,61 @@ struct ThriftDev {
         if (n > size - pos || pos > size) { err = true; pos = size; return; }
         pos += n;
     }
-    // Skip a value of type t (containers with an explicit stack).
+    // Skip a value of type t: containers on an explicit stack (no recursion), at most SKIP_DEPTH open at once.
+    // Every step of the outer loop either consumes a byte or closes a container: a scalar is at least a byte (a
+    // bool inside a list, set or map is one byte, as libthrift writes it; only a struct field's bool is in its
+    // field header, which was a byte), a list or map header is at least a byte, a struct opens for nothing but
+    // its next step reads a field header or its STOP, and advance() checks a binary against the bytes that
+    // remain. byte() fails at the chunk's end, so a skip ends within two steps per byte left, whatever the counts
+    // say (a list<struct> of 2^62 elements in a 40-byte chunk is refused after 40 of them).
     __device__ void skip(int t) {
-        struct Frame { int kind; uint64_t left; int et, vt, last; };   // kind 0 struct, 1 list/set, 2 map
-        Frame st[SKIP_DEPTH];
+        struct Frame { int kind; uint64_t left; int et, vt, last; };   // kind 0 struct (last: field id), 1 list/set,
+        Frame st[SKIP_DEPTH];                                          // 2 map (left: pairs; last: 1 = value is next)
         int sp = 0;
         int cur = t;
         for (;;) {
             if (err) return;
-            bool push = false;
             switch (cur) {
             case 1: case 2: break;
             case 3: byte(); break;
             case 4: case 5: case 6: uvarint(); break;
             case 7: advance(8); break;
             case 8: advance(uvarint()); break;
-            case 9: case 10: {
-                const uint32_t h = byte();
-                uint64_t n = h >> 4;
-                if (n == 15) n = uvarint();
-                st[sp] = Frame{1, n, int(h & 0xf), 0, 0};
-                push = true;
+            case 9: case 10: case 11: case 12: {
+                if (sp == SKIP_DEPTH) { err = true; return; }
+                Frame& f = st[sp++];
+                if (cur == 12) {
+                    f = Frame{0, 0, 0, 0, 0};
+                } else if (cur == 11) {
+                    const uint64_t n = uvarint();
+                    const uint32_t kv = n ? byte() : 0u;   // the empty map has no key / value type byte
+                    f = Frame{2, n, int(kv >> 4), int(kv & 0xf), 0};
+                } else {
+                    const uint32_t h = byte();
+                    uint64_t n = h >> 4;
+                    if (n == 15) n = uvarint();
+                    f = Frame{1, n, int(h & 0xf), 0, 0};
+                }
                 break;
             }
-            case 11: {
-                const uint64_t n = uvarint();
-                const uint32_t kv = n ? byte() : 0u;
-                st[sp] = Frame{2, 2 * n, int(kv >> 4), int(kv & 0xf), 0};
-                push = true;
-                break;
-            }
-            case 12: st[sp] = Frame{0, 0, 0, 0, 0}; push = true; break;
             default: err = true; return;
             }
-            if (push && ++sp > SKIP_DEPTH - 1) { err = true; return; }
             // next value to skip: from the innermost open container
             for (;;) {
                 if (sp == 0) return;
                 Frame& f = st[sp - 1];
                 if (f.kind == 0) {
-                    int ft = 0;
-                    if (field(f.last, ft) == 0) { sp--; if (err) return; continue; }
+                    int ft = 0, fid;
+                    if (!field(f.last, ft, fid)) { sp--; if (err) return; continue; }
                     cur = ft;
                 } else if (f.left == 0) {
                     sp--;
                     continue;
                 } else {
-                    const uint64_t k = f.left--;
-                    cur = f.kind == 1 ? f.et : ((k & 1) == 0 ? f.et : f.vt);
-                    if (f.kind == 1 && (cur == 1 || cur == 2)) { byte(); continue; }   // list bools are one byte
+                    if (f.kind == 1) { cur = f.et; f.left--; }
+                    else if (f.last == 0) { cur = f.et; f.last = 1; }
+                    else { cur = f.vt; f.last = 0; f.left--; }
+                    if (cur == 1 || cur == 2) cur = 3;   // a bool in a container: one byte
                 }
                 break;
             }
@@ -170,23 +177,23 @@ __global__ __launch_bounds__(64) void k_page_scan(const ScanChunk* __restrict__ 
         d.page_type = -1;
         uint32_t crc = 0;
         int has_crc = 0;
-        int last = 0, t = 0, id;
-        while ((id = r.field(last, t)) != 0) {
+        int last = 0, t = 0, id = 0;
+        while (r.field(last, t, id)) {
             if (id == 1) d.page_type = int32_t(r.integer(t));
             else if (id == 2) d.uncompressed_size = uint32_t(r.integer(t));
             else if (id == 3) d.compressed_size = uint32_t(r.integer(t));
             else if (id == 4 && t == 5) { crc = uint32_t(r.integer(t)); has_crc = 1; }
             else if ((id == 5 || id == 7 || id == 8) && t == 12) {
-                int l2 = 0, t2 = 0, i2;
-                while ((i2 = r.field(l2, t2)) != 0) {
+                int l2 = 0, t2 = 0, i2 = 0;
+                while (r.field(l2, t2, i2)) {
                     if (id == 5) {
                         if (i2 == 1) d.num_values = int32_t(r.integer(t2));
                         else if (i2 == 2) d.encoding = int32_t(r.integer(t2));
                         else if (i2 == 3) d.def_encoding = int32_t(r.integer(t2));
                         else if (i2 == 4) d.rep_encoding = int32_t(r.integer(t2));
                         else if (i2 == 5 && t2 == 12) {   // Statistics.null_count: a routing hint
-                            int l3 = 0, t3 = 0, i3;
-                            while ((i3 = r.field(l3, t3)) != 0) {
+                            int l3 = 0, t3 = 0, i3 = 0;
+                            while (r.field(l3, t3, i3)) {
                                 if (i3 == 3) {
                                     const int64_t nn = r.integer(t3);
                                     d.num_nulls = nn >= 0 && nn <= 0x7fffffff ? int32_t(nn) : -1;

@@ -35,6 +35,8 @@ with ParquetFile(path) as pf:
         npages += d.n_pages
     t_host = time.perf_counter() - t0
     nv = [sum(d.pages[i].num_values for i in range(d.n_pages) if d.pages[i].page_type != 2) for d in descs]
+    # the descriptors belong to the pf_file: copy them out before it closes
+    host_pages = [[tuple(getattr(d.pages[k], f) for f, _ in PageDesc._fields_) for k in range(d.n_pages)] for d in descs]
 dec = GpuDecoder(0)
 dptr = C.c_void_p()
 check(L.pf_device_alloc(dec.h, total, C.byref(dptr)), dec.h)
@@ -53,7 +55,7 @@ for crc in (0, 1):
         assert rc == 0, L.pf_last_error(dec.h)
     got = sum(res[i].n_pages for i in range(len(items)))
     assert got == npages
-    ok = all(all(getattr(pages[i * cap + k], f) == getattr(descs[i].pages[k], f) for f, _ in PageDesc._fields_)
+    ok = all(tuple(getattr(pages[i * cap + k], f) for f, _ in PageDesc._fields_) == host_pages[i][k]
              for i in range(len(items)) for k in range(res[i].n_pages))
     print(f"pf_scan_pages verify_crc={crc}: {len(items)} chunks, {got} pages, {total / 1e6:.1f} MB, "
           f"median {np.median(ts[1:]) * 1e3:.3f} ms (sync call incl. copies), descs match host walk: {ok}", flush=True)
