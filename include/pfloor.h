@@ -184,6 +184,28 @@ int pf_memcpy_h2d(pf_ctx* ctx, void* dst, const void* src, size_t bytes);   /* a
 int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks,
                         const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
 
+/* Windowed decode: chunk i's results are cut to rows [skip_rows, skip_rows + take_rows) of the pages listed (rows
+ * counted from the first row of its first data page; take_rows -1: to the end), on the GPU, before anything crosses the
+ * link. windows == NULL is pf_decode_row_group, call for call; otherwise one window per chunk. A negative skip_rows or
+ * a take_rows < -1 is PF_ERR_INVALID_ARG and nothing is enqueued. After pf_wait, pf_column_info_get, pf_copy_column and
+ * pf_copy_columns_async describe each chunk as if it had held only the window's rows, under the layout rules above:
+ * num_rows = take, num_entries / num_slots / num_values / num_chars those of the window, values from the window's first
+ * slot, validity and list_validity from bit 0 with the unused high bits of the last byte zero, offsets[0] = 0 and
+ * list_offsets[0] = 0, chars / def_levels / rep_levels only the window's (take 0: empty arrays, offsets = {0},
+ * list_offsets = {0}). Per-chunk status after pf_wait (the other chunks are unaffected): PF_ERR_INVALID_ARG when the
+ * window reaches past the rows the pages hold (for v1 and nested pages only the device knows that count);
+ * PF_ERR_CORRUPT_PAGE when the first entry of a max_rep = 1 chunk has a repetition level other than 0 (pages of an
+ * indexed chunk start at row boundaries); PF_ERR_UNSUPPORTED_TYPE for max_rep > 1 unless the window keeps every row.
+ * A window {0, -1} is the identity and costs nothing; any other window runs the window kernels (k_win_bounds,
+ * k_win_copy: pf_window.hip), which write into twin output arenas (a window that turns out to keep every row is left
+ * in place). The twins have the capacity of the decode arenas (the chars arena is at least 16 MiB) and stay allocated
+ * until pf_ctx_destroy, so a context that has decoded with windows once holds twice the output memory. After a decode in which any chunk had a window other than {0, -1}, pf_batch_bytes, pf_copy_batch_async
+ * and pf_column_info_host return PF_ERR_STATE: the arenas hold more than the windows, and compacting them into one
+ * batch layout is not done. */
+typedef struct pf_row_window { int64_t skip_rows; int64_t take_rows; } pf_row_window;   /* take_rows -1: to the end */
+int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const pf_row_window* windows,
+                             const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
+
 /* Block until the enqueued decode has finished; returns the first per-chunk error. */
 int pf_wait(pf_ctx* ctx);
 
@@ -210,7 +232,8 @@ int pf_copy_columns_async(pf_ctx* ctx, int n, const int* chunks, const pf_column
  * Valid after pf_wait until the next decode on this context. A mapped pinned buffer (pf_host_alloc,
  * hipHostMalloc) is written by a download kernel on a copy stream the context shares with its twin
  * (pf_ctx_create_shared), ordered after the decode, so the link carries uploads and downloads at
- * once (round 6); any other buffer takes SDMA copies on the context stream. */
+ * once (round 6); any other buffer takes SDMA copies on the context stream. All three return PF_ERR_STATE after a
+ * pf_decode_row_group_rows in which any chunk had a window other than {0, -1}: use pf_copy_column(s_async) there. */
 int pf_batch_bytes(pf_ctx* ctx, size_t* bytes);
 int pf_copy_batch_async(pf_ctx* ctx, void* host, size_t cap);
 int pf_column_info_host(pf_ctx* ctx, int chunk, const void* host, pf_column_info* out);
@@ -328,6 +351,32 @@ typedef struct pf_column_index {
  * PF_ERR_CORRUPT_PAGE if the struct is damaged (list lengths that disagree, a varint overrun, a size past the
  * range). Unknown fields (the level histograms) are skipped. */
 int pf_file_column_index(pf_file* f, int row_group, int column, pf_column_index* out);
+/* ---- reading a row range of a row group. pf_file_chunk_desc_rows selects the data pages that hold rows
+ *      [row_lo, row_hi) through the chunk's OffsetIndex and reads nothing else of the chunk: the index, the dictionary
+ *      page (the bytes between the chunk's start and the first page location) and the selected pages' file range.
+ *      `desc` describes a buffer that holds the dictionary range followed directly by the data range, starting at
+ *      offset_in_buffer (chunk_size = dict_size + data_size; page offsets are relative to that start; num_rows = the
+ *      rows the selected pages cover, from the index). The caller reads the two ranges into that buffer and passes
+ *      {skip_rows, take_rows} to pf_decode_row_group_rows. A chunk without an OffsetIndex gets the descriptor of
+ *      pf_file_chunk_desc (every page) with indexed = 0, first_row = 0, skip_rows = row_lo: the window still trims it.
+ *      0 <= row_lo <= row_hi <= RowGroup.num_rows, else PF_ERR_INVALID_ARG. An empty range selects no page (all sizes
+ *      0, first_row = row_lo). Headers are read at the locations the index gives, by the reader and with the limits of
+ *      pf_file_chunk_desc. PF_ERR_CORRUPT_PAGE: a location outside the chunk, locations or first_row_index not
+ *      increasing (the first row index must be 0), a compressed_page_size shorter than the header plus the stored body,
+ *      a location of no data page, v2 num_rows that disagree with the index. The page arrays are owned by the pf_file,
+ *      one per chunk, apart from those of pf_file_chunk_desc (valid until the next call for the same chunk). ---- */
+typedef struct pf_chunk_rows {
+    int32_t  indexed;        /* 1: pages were selected through the OffsetIndex; 0: the chunk has none, every page is listed */
+    int32_t  first_page;     /* index (among the chunk's data pages) of the first data page selected */
+    int32_t  n_data_pages;   /* data pages selected */
+    int64_t  first_row;      /* row (within the row group) of the first entry of the first selected data page */
+    int64_t  skip_rows;      /* row_lo - first_row */
+    int64_t  take_rows;      /* row_hi - row_lo */
+    uint64_t dict_start, dict_size;   /* file range of the dictionary page (header + body); size 0: none */
+    uint64_t data_start, data_size;   /* file range of the selected data pages (headers + bodies, contiguous) */
+} pf_chunk_rows;
+int pf_file_chunk_desc_rows(pf_file* f, int row_group, int column, int64_t row_lo, int64_t row_hi,
+                            uint64_t offset_in_buffer, pf_chunk_desc* desc, pf_chunk_rows* rows);
 const char* pf_file_created_by(pf_file* f);
 
 /* ---- write path: the reference's ParquetWriter (ParquetWriter.java:61-165: SNAPPY,

@@ -25,6 +25,7 @@ struct pf_file {
     pf::FileMeta meta;
     std::map<std::pair<int, int>, std::vector<pf_page_desc>> pages;
     std::map<std::pair<int, int>, pf::ColumnIndexMeta> column_indexes;
+    std::map<std::pair<int, int>, std::vector<pf_page_desc>> row_pages;   // pf_file_chunk_desc_rows (its own arrays)
 };
 
 extern "C" {
@@ -235,6 +236,128 @@ int pf_file_chunk_desc(pf_file* f, int rg, int col, uint64_t chunk_offset_in_buf
     d->chunk_offset = chunk_offset_in_buffer;
     d->chunk_size = size;
     d->num_rows = f->meta.row_groups[rg].num_rows;
+    return PF_OK;
+}
+
+int pf_file_chunk_desc_rows(pf_file* f, int rg, int col, int64_t row_lo, int64_t row_hi, uint64_t offset_in_buffer,
+                            pf_chunk_desc* d, pf_chunk_rows* rows) {
+    if (!d || !rows) return ferr(PF_ERR_INVALID_ARG, "null arg");
+    uint64_t start, size;
+    int rc = pf_file_chunk_range(f, rg, col, &start, &size);
+    if (rc) return rc;
+    const int64_t n_rows = f->meta.row_groups[rg].num_rows;
+    if (row_lo < 0 || row_lo > row_hi || row_hi > n_rows) return ferr(PF_ERR_INVALID_ARG, "row range outside the row group");
+    int64_t ci_off, oi_off;
+    int32_t ci_len, oi_len;
+    rc = pf_file_chunk_index_ranges(f, rg, col, &ci_off, &ci_len, &oi_off, &oi_len);
+    if (rc) return rc;
+    const pf::ChunkMeta& m = f->meta.row_groups[rg].columns[col];
+    const pf::LeafMeta& L = f->meta.leaves[col];
+    std::memset(rows, 0, sizeof(*rows));
+    if (oi_off < 0 || m.num_values <= 0) {   // no OffsetIndex: every page, the window does the rest
+        rc = pf_file_chunk_desc(f, rg, col, offset_in_buffer, d);
+        if (rc) return rc;
+        for (int i = 0; i < d->n_pages; i++) rows->n_data_pages += d->pages[i].page_type != PF_PAGE_DICTIONARY;
+        rows->skip_rows = row_lo;
+        rows->take_rows = row_hi - row_lo;
+        rows->data_start = start;
+        rows->data_size = size;
+        return PF_OK;
+    }
+    std::vector<pf_page_desc> built;   // swapped in on success: a failed call leaves the earlier descriptor's array alone
+    int64_t covered = 0;
+    try {
+        std::vector<uint8_t> buf;
+        buf.resize(size_t(oi_len));
+        rc = pf_file_read(f, uint64_t(oi_off), uint64_t(oi_len), buf.data());
+        if (rc) return rc;
+        std::vector<pf_page_location> locs;
+        pf::parse_offset_index(buf.data(), buf.size(), locs);
+        const size_t np = locs.size();
+        if (np == 0 || np > size_t(INT32_MAX)) throw pf::MetaError("page locations: none, or too many");
+        uint64_t prev_end = start;
+        for (size_t p = 0; p < np; p++) {
+            const pf_page_location& a = locs[p];
+            if (uint64_t(a.offset) < prev_end || uint64_t(a.offset) > start + size ||
+                uint64_t(a.compressed_page_size) > start + size - uint64_t(a.offset))
+                throw pf::MetaError("page location outside the chunk, or not increasing");
+            prev_end = uint64_t(a.offset) + uint64_t(a.compressed_page_size);
+            if (p == 0 ? a.first_row_index != 0 : a.first_row_index <= locs[p - 1].first_row_index)
+                throw pf::MetaError("page location first_row_index not increasing from 0");
+            if (a.first_row_index >= n_rows) throw pf::MetaError("page location first_row_index past the row group");
+        }
+        auto row_end = [&](size_t p) { return p + 1 < np ? locs[p + 1].first_row_index : n_rows; };
+        rows->indexed = 1;
+        rows->first_row = row_lo;
+        rows->take_rows = row_hi - row_lo;
+        size_t p0 = 0, p1 = 0;   // [p0, p1)
+        if (row_lo < row_hi) {
+            while (row_end(p0) <= row_lo) p0++;
+            p1 = p0;
+            while (p1 < np && locs[p1].first_row_index < row_hi) p1++;
+            rows->first_page = int32_t(p0);
+            rows->n_data_pages = int32_t(p1 - p0);
+            rows->first_row = locs[p0].first_row_index;
+            rows->skip_rows = row_lo - rows->first_row;
+            rows->dict_start = start;
+            rows->dict_size = uint64_t(locs[0].offset) - start;
+            rows->data_start = uint64_t(locs[p0].offset);
+            rows->data_size = uint64_t(locs[p1 - 1].offset) + uint64_t(locs[p1 - 1].compressed_page_size) - rows->data_start;
+            covered = row_end(p1 - 1) - rows->first_row;
+        }
+        buf.resize(size_t(rows->dict_size + rows->data_size));
+        if (rows->dict_size) {
+            rc = pf_file_read(f, rows->dict_start, rows->dict_size, buf.data());
+            if (rc) return rc;
+            pf_page_desc pd;
+            const size_t h = pf::read_page_header(buf.data(), size_t(rows->dict_size), pd);
+            if (pd.page_type != PF_PAGE_DICTIONARY || int32_t(pd.compressed_size) < 0 ||
+                uint64_t(h) + pd.compressed_size > rows->dict_size)
+                throw pf::MetaError("no dictionary page before the first page location");
+            pd.offset = h;
+            built.push_back(pd);
+        }
+        if (rows->data_size) {
+            rc = pf_file_read(f, rows->data_start, rows->data_size, buf.data() + rows->dict_size);
+            if (rc) return rc;
+        }
+        for (size_t p = p0; p < p1; p++) {
+            const uint64_t at = rows->dict_size + (uint64_t(locs[p].offset) - rows->data_start);
+            const uint64_t cps = uint64_t(locs[p].compressed_page_size);
+            pf_page_desc pd;
+            const size_t h = pf::read_page_header(buf.data() + at, size_t(cps), pd);
+            if (int32_t(pd.compressed_size) < 0 || uint64_t(h) + pd.compressed_size > cps)
+                throw pf::MetaError("compressed_page_size shorter than the page");
+            if (pd.page_type != PF_PAGE_DATA && pd.page_type != PF_PAGE_DATA_V2) throw pf::MetaError("page location of no data page");
+            if (pd.num_values < 0) throw pf::MetaError("negative num_values");
+            if (pd.page_type == PF_PAGE_DATA_V2) {
+                if (pd.def_bytes < 0 || pd.rep_bytes < 0 || uint64_t(pd.def_bytes) + uint64_t(pd.rep_bytes) > pd.compressed_size ||
+                    uint64_t(pd.def_bytes) + uint64_t(pd.rep_bytes) > pd.uncompressed_size)
+                    throw pf::MetaError("v2 level lengths exceed page");
+                if (int64_t(pd.num_rows) != row_end(p) - locs[p].first_row_index)
+                    throw pf::MetaError("v2 num_rows disagrees with the OffsetIndex");
+            }
+            pd.offset = at + h;
+            built.push_back(pd);
+        }
+    } catch (const std::exception& e) {
+        return ferr(PF_ERR_CORRUPT_PAGE, e.what());
+    }
+    auto& pages = f->row_pages[{rg, col}];
+    pages.swap(built);
+    std::memset(d, 0, sizeof(*d));
+    d->physical_type = L.physical_type;
+    d->type_length = L.type_length;
+    d->max_def = L.max_def;
+    d->max_rep = L.max_rep;
+    d->repeated_def = L.repeated_def;
+    d->list_null_def = L.list_null_def;
+    d->codec = m.codec;
+    d->n_pages = int32_t(pages.size());
+    d->pages = pages.empty() ? nullptr : pages.data();
+    d->chunk_offset = offset_in_buffer;
+    d->chunk_size = rows->dict_size + rows->data_size;
+    d->num_rows = covered;
     return PF_OK;
 }
 

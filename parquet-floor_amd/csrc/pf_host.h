@@ -66,6 +66,9 @@ struct ColumnIndexMeta {
 // a length past the range, list lengths that disagree, a missing required field); never reads outside the range.
 void parse_column_index(const uint8_t* p, size_t n, ColumnIndexMeta& out);
 void parse_offset_index(const uint8_t* p, size_t n, std::vector<pf_page_location>& out);
+// One Thrift compact PageHeader at [p, p + n): fills d (offset 0) and returns the header's length; MetaError when
+// damaged. The reader and the limits (PF_THRIFT_MAX_NESTING) of FileMeta::walk_pages, which calls it per page.
+size_t read_page_header(const uint8_t* p, size_t n, pf_page_desc& d);
 
 // Statistics of a page or a chunk as the write path serialises them (parquet.thrift Statistics: 3 null_count,
 // 5 max_value, 6 min_value; the legacy 1 max / 2 min only where `legacy` says so).

@@ -320,6 +320,25 @@ struct DevChunkResult {
     int32_t err_page;
 };
 
+// Row windows (pf_window.hip, pf_decode_row_group_rows): one DevWin per chunk whose window is not {0, -1}, and what
+// k_win_bounds finds for it. k_win_copy writes the window's arrays into the twin output arenas (out, bits, chars: the
+// decode arenas' sizes and per-chunk offsets), in tiles of WIN_TILE output bytes per array.
+constexpr uint32_t WIN_TILE = 4096;
+struct DevWin {
+    int32_t chunk, pad;
+    int64_t skip, take;       // rows from the first row of the first data page; take -1: to the end
+};
+struct DevWinRes {
+    int64_t e0, n_entries;    // the window's first level entry, and how many it has
+    int64_t s0, n_slots;
+    int64_t c0, n_chars;
+    int64_t n_values, n_rows;
+    const uint8_t* chars_src; // the chunk's chars (k_scan placed them) and their twin
+    uint8_t* chars_dst;
+    int32_t status;           // pf_status of the window (the decode's own status when that failed)
+    int32_t identity;         // 1: the window keeps every row; nothing was copied, the decode arenas hold the result
+};
+
 // GPU page-header scan (pf_scan.hip, pf_scan_pages)
 struct ScanChunk {            // device copy of pf_scan_chunk
     const uint8_t* base;      // chunk's first byte

@@ -60,6 +60,11 @@ void launch_delta(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list,
 void launch_dlen(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
 void launch_dba_chars(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
 
+// pf_window.hip: out_delta / bits_delta = twin arena base - decode arena base (bytes)
+void launch_window(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWin* d_wins, DevWinRes* d_wres, int n_wins,
+                   int copy_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
+                   hipStream_t st);
+
 // pf_scan.hip
 void launch_page_scan(const ScanChunk* d_chunks, int n_chunks, pf_page_desc* d_pages, ScanCrc* d_crcs, ScanResult* d_res,
                       hipStream_t s);

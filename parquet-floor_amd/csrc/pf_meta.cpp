@@ -345,6 +345,56 @@ void parse_offset_index(const uint8_t* p, size_t n, std::vector<pf_page_location
     if (!have) ThriftReader::fail("offset index without page locations");
 }
 
+// One Thrift compact PageHeader at [p, p + n): fills d (offset left 0) and returns the header's length. The reader
+// and the limits of every page walk (walk_pages, pf_file_chunk_desc_rows).
+size_t read_page_header(const uint8_t* p, size_t n, pf_page_desc& d) {
+    ThriftReader r{p, p + n, PF_THRIFT_MAX_NESTING};
+    d = pf_page_desc{};
+    d.is_compressed = 1;
+    d.num_nulls = -1;   // v1 without page statistics: unknown
+    d.page_type = -1;
+    int last = 0, id, t;
+    while (r.field(last, id, t)) {
+        if (id == 1) d.page_type = int(r.integer(t));
+        else if (id == 2) d.uncompressed_size = uint32_t(r.integer(t));
+        else if (id == 3) d.compressed_size = uint32_t(r.integer(t));
+        else if ((id == 5 || id == 7 || id == 8) && t == 12) {
+            int l2 = 0, i2, t2;
+            while (r.field(l2, i2, t2)) {
+                if (id == 5) {          // DataPageHeader
+                    if (i2 == 1) d.num_values = int32_t(r.integer(t2));
+                    else if (i2 == 2) d.encoding = int32_t(r.integer(t2));
+                    else if (i2 == 3) d.def_encoding = int32_t(r.integer(t2));
+                    else if (i2 == 4) d.rep_encoding = int32_t(r.integer(t2));
+                    else if (i2 == 5 && t2 == 12) {   // Statistics: null_count (field 3), a routing hint
+                        int l3 = 0, i3, t3;
+                        while (r.field(l3, i3, t3)) {
+                            if (i3 == 3) {
+                                const int64_t nn = r.integer(t3);
+                                d.num_nulls = nn >= 0 && nn <= INT32_MAX ? int32_t(nn) : -1;
+                            } else r.skip(t3);
+                        }
+                    } else r.skip(t2);
+                } else if (id == 7) {   // DictionaryPageHeader
+                    if (i2 == 1) d.num_values = int32_t(r.integer(t2));
+                    else if (i2 == 2) d.encoding = int32_t(r.integer(t2));
+                    else r.skip(t2);
+                } else {                // DataPageHeaderV2
+                    if (i2 == 1) d.num_values = int32_t(r.integer(t2));
+                    else if (i2 == 2) d.num_nulls = int32_t(r.integer(t2));
+                    else if (i2 == 3) d.num_rows = int32_t(r.integer(t2));
+                    else if (i2 == 4) d.encoding = int32_t(r.integer(t2));
+                    else if (i2 == 5) d.def_bytes = int32_t(r.integer(t2));
+                    else if (i2 == 6) d.rep_bytes = int32_t(r.integer(t2));
+                    else if (i2 == 7) d.is_compressed = r.boolean(t2) ? 1 : 0;
+                    else r.skip(t2);
+                }
+            }
+        } else r.skip(t);
+    }
+    return size_t(r.p - p);
+}
+
 // Page headers of one chunk: parquet-mr Chunk.readAllPages reads pages until the chunk's
 // num_values level entries have been seen; INDEX and unknown page types are skipped.
 void FileMeta::walk_pages(const uint8_t* chunk, size_t size, const ChunkMeta& m, std::vector<pf_page_desc>& out) {
@@ -353,51 +403,8 @@ void FileMeta::walk_pages(const uint8_t* chunk, size_t size, const ChunkMeta& m,
     size_t off = 0;
     bool have_dict = false;
     while (seen < m.num_values) {
-        ThriftReader r{chunk + off, chunk + size, PF_THRIFT_MAX_NESTING};
-        pf_page_desc d{};
-        d.is_compressed = 1;
-        d.num_nulls = -1;   // v1 without page statistics: unknown
-        d.page_type = -1;
-        int last = 0, id, t;
-        while (r.field(last, id, t)) {
-            if (id == 1) d.page_type = int(r.integer(t));
-            else if (id == 2) d.uncompressed_size = uint32_t(r.integer(t));
-            else if (id == 3) d.compressed_size = uint32_t(r.integer(t));
-            else if ((id == 5 || id == 7 || id == 8) && t == 12) {
-                int l2 = 0, i2, t2;
-                while (r.field(l2, i2, t2)) {
-                    if (id == 5) {          // DataPageHeader
-                        if (i2 == 1) d.num_values = int32_t(r.integer(t2));
-                        else if (i2 == 2) d.encoding = int32_t(r.integer(t2));
-                        else if (i2 == 3) d.def_encoding = int32_t(r.integer(t2));
-                        else if (i2 == 4) d.rep_encoding = int32_t(r.integer(t2));
-                        else if (i2 == 5 && t2 == 12) {   // Statistics: null_count (field 3), a routing hint
-                            int l3 = 0, i3, t3;
-                            while (r.field(l3, i3, t3)) {
-                                if (i3 == 3) {
-                                    const int64_t nn = r.integer(t3);
-                                    d.num_nulls = nn >= 0 && nn <= INT32_MAX ? int32_t(nn) : -1;
-                                } else r.skip(t3);
-                            }
-                        } else r.skip(t2);
-                    } else if (id == 7) {   // DictionaryPageHeader
-                        if (i2 == 1) d.num_values = int32_t(r.integer(t2));
-                        else if (i2 == 2) d.encoding = int32_t(r.integer(t2));
-                        else r.skip(t2);
-                    } else {                // DataPageHeaderV2
-                        if (i2 == 1) d.num_values = int32_t(r.integer(t2));
-                        else if (i2 == 2) d.num_nulls = int32_t(r.integer(t2));
-                        else if (i2 == 3) d.num_rows = int32_t(r.integer(t2));
-                        else if (i2 == 4) d.encoding = int32_t(r.integer(t2));
-                        else if (i2 == 5) d.def_bytes = int32_t(r.integer(t2));
-                        else if (i2 == 6) d.rep_bytes = int32_t(r.integer(t2));
-                        else if (i2 == 7) d.is_compressed = r.boolean(t2) ? 1 : 0;
-                        else r.skip(t2);
-                    }
-                }
-            } else r.skip(t);
-        }
-        size_t body = size_t(r.p - chunk);
+        pf_page_desc d;
+        size_t body = off + read_page_header(chunk + off, size - off, d);
         if (int32_t(d.compressed_size) < 0 || body + d.compressed_size > size) throw MetaError("page body exceeds chunk");
         d.offset = body;
         off = body + d.compressed_size;

@@ -197,6 +197,13 @@ struct pf_ctx {
     HostBuf h_enc_px;                      // pf_encode_chunk: the page index block D2H (pf_encoded_chunk.index_*)
     std::vector<int64_t> h_enc_pgoff, h_enc_pgrow;   // pf_encoded_chunk.page_offset / page_first_row
     std::vector<int32_t> h_enc_pgsize;               // pf_encoded_chunk.page_size
+    // row windows (pf_decode_row_group_rows): the chunks whose window is not {0, -1}, their tables, and the twin output
+    // arenas k_win_copy writes (allocated only for a batch that has such a window)
+    std::vector<DevWin> wins;
+    DevBuf d_win, d_wout, d_wbits, d_wchars;
+    HostBuf h_win;                         // DevWin[n] up, DevWinRes[n] down
+    int win_grid = 1;
+    hipEvent_t ev_win[2] = {};
 };
 
 namespace {
@@ -304,6 +311,20 @@ int enqueue_kernels(pf_ctx* ctx) {
     launch_nest_decode(d_chunks, d_pages, pairs(L_NSEG), n_nseg, d_res, st);
     launch_dba_chars(d_chunks, d_pages, list(L_DBA), len(L_DBA), d_res, st);
     EVREC(ctx, ctx->ev[10], st);
+    if (!ctx->wins.empty()) {   // row windows: after every decode stage, so a chars rerun trims again
+        const int nw = int(ctx->wins.size());
+        const size_t res_off = align_up(sizeof(DevWin) * nw, 256);
+        DevWin* d_wins = static_cast<DevWin*>(ctx->d_win.p);
+        DevWinRes* d_wres = reinterpret_cast<DevWinRes*>(static_cast<uint8_t*>(ctx->d_win.p) + res_off);
+        EVREC(ctx, ctx->ev_win[0], st);
+        launch_window(d_chunks, d_res, d_wins, d_wres, nw, ctx->win_grid, static_cast<const uint8_t*>(ctx->d_chars.p),
+                      static_cast<uint8_t*>(ctx->d_wchars.p),
+                      static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p),
+                      static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p), st);
+        EVREC(ctx, ctx->ev_win[1], st);
+        HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_win.p) + res_off, d_wres, sizeof(DevWinRes) * nw,
+                                   hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(ctx, hipGetLastError());
     // results + device-written chunk fields (chars base) back to pinned host memory
     const size_t res_pad = align_up(sizeof(DevChunkResult) * ctx->n_chunks, 256);
@@ -1313,6 +1334,7 @@ int ctx_init(pf_ctx* ctx, pf_ctx* peer) {
     HIPCHK(nullptr, hipEventCreateWithFlags(&ctx->ev_dl, hipEventDisableTiming));
     for (auto& e : ctx->ev) HIPCHK(nullptr, hipEventCreate(&e));
     for (auto& e : ctx->ev_bloom) HIPCHK(nullptr, hipEventCreate(&e));
+    for (auto& e : ctx->ev_win) HIPCHK(nullptr, hipEventCreate(&e));
     return PF_OK;
 }
 
@@ -1360,8 +1382,10 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // this context's work and any peer's ahead of it
     if (ctx->copies_pending) (void)hipEventSynchronize(ctx->ev_copy);   // (a download on the copy stream)
     for (DevBuf* b : {&ctx->d_in, &ctx->d_scratch, &ctx->d_out, &ctx->d_bits, &ctx->d_chars, &ctx->d_meta, &ctx->d_tokmap,
-                      &ctx->d_scan_in, &ctx->d_scan, &ctx->d_enc, &ctx->d_enc_sec, &ctx->d_enc_out})
+                      &ctx->d_scan_in, &ctx->d_scan, &ctx->d_enc, &ctx->d_enc_sec, &ctx->d_enc_out, &ctx->d_win, &ctx->d_wout,
+                      &ctx->d_wbits, &ctx->d_wchars})
         b->release();
+    ctx->h_win.release();
     ctx->h_meta.release();
     ctx->h_res.release();
     ctx->h_enc_slots.release();
@@ -1370,6 +1394,7 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_enc_bloom.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_bloom) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->ev_win) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
     if (ctx->ev_dl) (void)hipEventDestroy(ctx->ev_dl);
@@ -1408,11 +1433,13 @@ int pf_memcpy_h2d(pf_ctx* ctx, void* dst, const void* src, size_t bytes) {
     return PF_OK;
 }
 
-int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
-                        int bytes_on_device) {
-    if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
-    if (n_chunks < 0 || (n_chunks > 0 && (!cds || !bytes))) return fail(ctx, PF_ERR_INVALID_ARG, "bad arguments");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+}  // extern "C"
+
+namespace {
+// Plan, upload and enqueue one batch; ctx->wins lists the chunks to be windowed.
+int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
+                  int bytes_on_device) {
+    const bool windowed = !ctx->wins.empty();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // diagnostics: PF_DEBUG_PLAN=1 prints the host time of each phase (microseconds)
@@ -1442,8 +1469,11 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
     mark();
     // ---- arenas ----
     const size_t chars_cap = std::max<size_t>(size_t(2 * p.chars_hint) + (16u << 20), ctx->chars_need);
+    // (the window kernels read validity bits in 8-byte words: room for the last one)
+    const size_t bits_cap = std::max<size_t>(p.bits_bytes, 1) + (windowed ? 8 : 0);
     if (ctx->copies_pending) {
-        if (p.out_bytes > ctx->d_out.cap || p.bits_bytes > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap)
+        if (p.out_bytes > ctx->d_out.cap || bits_cap > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap ||
+            (windowed && (ctx->d_out.cap > ctx->d_wout.cap || ctx->d_bits.cap > ctx->d_wbits.cap || ctx->d_chars.cap > ctx->d_wchars.cap)))
             HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // a growing output arena must not be freed under a pending D2H copy
         else
             HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_copy, 0));   // (a download on the copy stream reads the arenas)
@@ -1451,8 +1481,26 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
     ctx->copies_pending = false;
     HIPCHK(ctx, ctx->d_scratch.ensure(std::max<size_t>(p.scratch_bytes, 1)));
     HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(p.out_bytes, 1)));
-    HIPCHK(ctx, ctx->d_bits.ensure(std::max<size_t>(p.bits_bytes, 1)));
+    HIPCHK(ctx, ctx->d_bits.ensure(bits_cap));
     HIPCHK(ctx, ctx->d_chars.ensure(chars_cap));
+    if (windowed) {   // the twins: the decode arenas' sizes, so a chunk keeps its offsets
+        const int nw = int(ctx->wins.size());
+        const size_t tab = align_up(sizeof(DevWin) * nw, 256) + sizeof(DevWinRes) * nw;
+        HIPCHK(ctx, ctx->d_wout.ensure(ctx->d_out.cap));
+        HIPCHK(ctx, ctx->d_wbits.ensure(ctx->d_bits.cap));
+        HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
+        HIPCHK(ctx, ctx->d_win.ensure(tab));
+        HIPCHK(ctx, ctx->h_win.ensure(tab));
+        std::memcpy(ctx->h_win.p, ctx->wins.data(), sizeof(DevWin) * nw);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win.p, ctx->h_win.p, sizeof(DevWin) * nw, hipMemcpyHostToDevice, st));
+        uint64_t tiles = 1;   // k_win_copy's workgroups per chunk stride over its tiles: a bound from the host's counts
+        for (const DevWin& w : ctx->wins) {
+            const DevChunk& ck = p.chunks[size_t(w.chunk)];
+            const uint64_t n = ck.max_rep == 0 && w.take >= 0 ? uint64_t(w.take) : uint64_t(ck.num_entries);
+            tiles = std::max<uint64_t>(tiles, n * uint64_t(std::max(ck.width, 8)) / WIN_TILE + 8);
+        }
+        ctx->win_grid = int(std::min<uint64_t>(tiles, 512));
+    }
     HIPCHK(ctx, ctx->d_tokmap.ensure(p.snap.tokmap_bytes));
     HIPCHK(ctx, ctx->d_meta.ensure(p.meta_bytes));
     HIPCHK(ctx, ctx->h_meta.ensure(p.meta_bytes));
@@ -1480,6 +1528,50 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
     return PF_OK;
 }
 
+// pf_decode_row_group (windows == nullptr) and pf_decode_row_group_rows.
+int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows, const uint8_t* bytes,
+                 size_t n_bytes, int bytes_on_device) {
+    if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
+    if (n_chunks < 0 || (n_chunks > 0 && (!cds || !bytes))) return fail(ctx, PF_ERR_INVALID_ARG, "bad arguments");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+    for (int c = 0; windows && c < n_chunks; c++)
+        if (windows[c].skip_rows < 0 || windows[c].take_rows < -1)
+            return fail(ctx, PF_ERR_INVALID_ARG, "row window: negative skip_rows, or take_rows below -1");
+    ctx->wins.clear();
+    for (int c = 0; windows && c < n_chunks; c++)
+        if (windows[c].skip_rows != 0 || windows[c].take_rows != -1)
+            ctx->wins.push_back(DevWin{c, 0, windows[c].skip_rows, windows[c].take_rows});
+    const int rc = enqueue_batch(ctx, cds, n_chunks, bytes, n_bytes, bytes_on_device);
+    if (rc) ctx->wins.clear();   // nothing windowed is pending: the batch-copy gates must not answer for this call
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
+                        int bytes_on_device) {
+    return decode_batch(ctx, cds, n_chunks, nullptr, bytes, n_bytes, bytes_on_device);
+}
+
+int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows,
+                             const uint8_t* bytes, size_t n_bytes, int bytes_on_device) {
+    return decode_batch(ctx, cds, n_chunks, windows, bytes, n_bytes, bytes_on_device);
+}
+
+// Diagnostics (not part of pfloor.h): the window stage of the last finished decode. *ms: time of its kernels (HIP
+// events; 0 when the decode had no window or stage timing is off; not a stage of pf_last_timing, whose stages are
+// the same with and without windows). *reruns: how often pf_wait ran the batch again for a chars overflow (0 or 1).
+int pf_debug_window(pf_ctx* ctx, float* ms, int* reruns) {
+    if (!ctx || !ms || !reruns) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    *ms = 0;
+    *reruns = ctx->reruns;
+    if (!ctx->timing_valid || !ctx->timing || ctx->wins.empty()) return PF_OK;
+    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev_win[0], ctx->ev_win[1]));
+    return PF_OK;
+}
+
 int pf_wait(pf_ctx* ctx) {
     if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
     if (!ctx->pending) return fail(ctx, PF_ERR_STATE, "nothing to wait for");
@@ -1502,6 +1594,7 @@ int pf_wait(pf_ctx* ctx) {
             ctx->reruns++;
             ctx->chars_need = size_t(need) + (1u << 20);
             HIPCHK(ctx, ctx->d_chars.ensure(ctx->chars_need));
+            if (!ctx->wins.empty()) HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
             int rc = upload_meta(ctx);
             if (rc) { ctx->pending = false; return rc; }
             rc = enqueue_kernels(ctx);
@@ -1509,6 +1602,9 @@ int pf_wait(pf_ctx* ctx) {
             continue;
         }
         int first_err = PF_OK;
+        size_t wi = 0;
+        const DevWinRes* wr = ctx->wins.empty() ? nullptr : reinterpret_cast<const DevWinRes*>(
+            static_cast<const uint8_t*>(ctx->h_win.p) + align_up(sizeof(DevWin) * ctx->wins.size(), 256));
         for (int c = 0; c < ctx->n_chunks; c++) {
             pf_column_info& ci = ctx->info[c];
             const DevChunk& ck = ctx->plan.chunks[c];
@@ -1527,6 +1623,28 @@ int pf_wait(pf_ctx* ctx) {
             ci.d_list_validity = ck.list_validity;
             ci.d_def_levels = ck.def_levels;
             ci.d_rep_levels = ck.rep_levels;
+            if (wi < ctx->wins.size() && ctx->wins[wi].chunk == c) {   // the window's view (chunks ascend in wins)
+                const DevWinRes& w = wr[wi++];
+                if (ci.status == 0 && w.status != 0) ci.status = w.status;
+                else if (ci.status == 0 && !w.identity) {
+                    const ptrdiff_t od = static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p);
+                    const ptrdiff_t bd = static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p);
+                    auto tw = [](auto* q, ptrdiff_t d) { return q ? reinterpret_cast<decltype(q)>(reinterpret_cast<uint8_t*>(q) + d) : nullptr; };
+                    ci.num_entries = w.n_entries;
+                    ci.num_slots = w.n_slots;
+                    ci.num_values = w.n_values;
+                    ci.num_rows = w.n_rows;
+                    ci.num_chars = ck.ptype == PF_BYTE_ARRAY ? w.n_chars : 0;
+                    ci.d_values = tw(ck.values, od);
+                    ci.d_validity = tw(ck.validity, bd);
+                    ci.d_offsets = tw(ck.offsets, od);
+                    ci.d_chars = w.chars_dst;
+                    ci.d_list_offsets = tw(ck.list_offsets, od);
+                    ci.d_list_validity = tw(ck.list_validity, bd);
+                    ci.d_def_levels = tw(ck.def_levels, od);
+                    ci.d_rep_levels = tw(ck.rep_levels, od);
+                }
+            }
             if (ci.status != 0 && first_err == PF_OK) {
                 first_err = ci.status;
                 char buf[160];
@@ -1646,6 +1764,7 @@ int pf_batch_bytes(pf_ctx* ctx, size_t* bytes) {
     if (!ctx || !bytes) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
+    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
     *bytes = batch_layout(ctx).total;
     return PF_OK;
 }
@@ -1654,6 +1773,7 @@ int pf_copy_batch_async(pf_ctx* ctx, void* host, size_t cap) {
     if (!ctx || (!host && cap)) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
+    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
     const BatchLayout b = batch_layout(ctx);
     if (b.total > cap) return fail(ctx, PF_ERR_CAPACITY, "batch buffer too small (pf_batch_bytes)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1703,6 +1823,7 @@ int pf_column_info_host(pf_ctx* ctx, int chunk, const void* host, pf_column_info
     if (!ctx || !out || !host) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
+    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
     const BatchLayout b = batch_layout(ctx);
     const uint8_t* h = static_cast<const uint8_t*>(host);
     auto rebase = [&](const void* p) -> const void* {

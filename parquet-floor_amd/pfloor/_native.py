@@ -83,6 +83,17 @@ class ColumnIndex(C.Structure):
                 ("value_off", C.POINTER(C.c_uint32))]
 
 
+class ChunkRows(C.Structure):
+    _fields_ = [("indexed", C.c_int32), ("first_page", C.c_int32), ("n_data_pages", C.c_int32),
+                ("first_row", C.c_int64), ("skip_rows", C.c_int64), ("take_rows", C.c_int64),
+                ("dict_start", C.c_uint64), ("dict_size", C.c_uint64), ("data_start", C.c_uint64),
+                ("data_size", C.c_uint64)]
+
+
+class RowWindow(C.Structure):
+    _fields_ = [("skip_rows", C.c_int64), ("take_rows", C.c_int64)]
+
+
 class PfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -137,6 +148,8 @@ def _load(path):
         "pf_device_free": ([vp, vp], C.c_int),
         "pf_memcpy_h2d": ([vp, vp, vp, sz], C.c_int),
         "pf_decode_row_group": ([vp, C.POINTER(ChunkDesc), i32, vp, sz, i32], C.c_int),
+        "pf_decode_row_group_rows": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), vp, sz, i32], C.c_int),
+        "pf_debug_window": ([vp, C.POINTER(C.c_float), C.POINTER(C.c_int)], C.c_int),   # (diagnostics, not in pfloor.h)
         "pf_wait": ([vp], C.c_int),
         "pf_column_info_get": ([vp, i32, C.POINTER(ColumnInfo)], C.c_int),
         "pf_copy_column": ([vp, i32, C.POINTER(ColumnOut)], C.c_int),
@@ -160,6 +173,8 @@ def _load(path):
         "pf_file_row_group_rows": ([vp, i32, i64p], C.c_int),
         "pf_file_chunk_range": ([vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
         "pf_file_chunk_desc": ([vp, i32, i32, C.c_uint64, C.POINTER(ChunkDesc)], C.c_int),
+        "pf_file_chunk_desc_rows": ([vp, i32, i32, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(ChunkDesc),
+                                     C.POINTER(ChunkRows)], C.c_int),
         "pf_file_read": ([vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "pf_file_chunk_bloom": ([vp, i32, i32, i64p, C.POINTER(C.c_int32)], C.c_int),
         "pf_file_chunk_index_ranges": ([vp, i32, i32, i64p, C.POINTER(C.c_int32), i64p, C.POINTER(C.c_int32)], C.c_int),

@@ -7,8 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import (ChunkDesc, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, PageLocation, ScanChunk,
-                      ScanResult, check, lib)
+from ._native import (ChunkDesc, ChunkRows, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, PageLocation,
+                      RowWindow, ScanChunk, ScanResult, check, lib)
 
 CONVERTED_UTF8, CONVERTED_ENUM, CONVERTED_JSON = 0, 4, 19
 LOGICAL_STRING, LOGICAL_ENUM, LOGICAL_JSON = 1, 4, 12
@@ -96,6 +96,77 @@ class ParquetFile:
         d = ChunkDesc()
         check(lib().pf_file_chunk_desc(self.h, rg, col, offset_in_buffer, C.byref(d)), None, f"pages rg{rg} c{col}")
         return d
+
+    def chunk_desc_rows(self, rg, col, lo, hi, offset_in_buffer):
+        """(ChunkDesc, ChunkRows) for rows [lo, hi) of a row group (pf_file_chunk_desc_rows): the data pages the
+        OffsetIndex selects and the dictionary page, laid out as one buffer range that starts at offset_in_buffer;
+        {skip_rows, take_rows} is the window GpuDecoder.decode takes. Every page of a chunk without an OffsetIndex."""
+        d, r = ChunkDesc(), ChunkRows()
+        check(lib().pf_file_chunk_desc_rows(self.h, rg, col, lo, hi, offset_in_buffer, C.byref(d), C.byref(r)), None,
+              f"pages rg{rg} c{col} rows [{lo}, {hi})")
+        return d, r
+
+    def plan_rows(self, rg, columns, lo, hi, align=256):
+        """Rows [lo, hi) of row group rg: every chunk's two file ranges (dictionary page, selected data pages) laid
+        out back to back in one buffer. Returns ([(col, ChunkDesc, ChunkRows, offset_in_buffer)], total bytes,
+        windows [(skip, take)]); read [dict_start, +dict_size) to offset_in_buffer and [data_start, +data_size)
+        directly behind it (read_rows does)."""
+        items, windows = [], []
+        off = 0
+        for col in columns:
+            d, r = self.chunk_desc_rows(rg, col, lo, hi, off)
+            items.append((col, d, r, off))
+            windows.append((r.skip_rows, r.take_rows))
+            off += (r.dict_size + r.data_size + align - 1) // align * align
+        return items, off, windows
+
+    def read_rows(self, items, base_ptr):
+        """The file ranges of plan_rows' items into the buffer at base_ptr. Returns the bytes read."""
+        n = 0
+        for _col, _d, r, off in items:
+            if r.dict_size:
+                self.read_into(r.dict_start, r.dict_size, base_ptr + off)
+            if r.data_size:
+                self.read_into(r.data_start, r.data_size, base_ptr + off + r.dict_size)
+            n += r.dict_size + r.data_size
+        return n
+
+    def candidate_rows(self, rg, col, lo=None, hi=None):
+        """The ascending, disjoint, merged (row_lo, row_hi) ranges of the data pages that may hold a value v with
+        lo <= v <= hi (None: unbounded), from the page index alone. A page is dropped only if it is a null page, or
+        its max < lo, or its min > hi. INT32 / INT64 compare as signed integers (lo, hi: int); BYTE_ARRAY compares
+        unsigned bytewise, a proper prefix first (lo, hi: bytes) -- truncated bounds are still bounds. Other types
+        raise ValueError. [(0, rows)] for a chunk without a ColumnIndex or without an OffsetIndex."""
+        pt = self.columns[col].physical_type
+        if pt not in (1, 2, 6):
+            raise ValueError(f"candidate_rows: unsupported physical type {pt}")
+        rows = self.row_group_rows(rg)
+        px = self.page_index(rg, col)
+        oi, ci = px["offset_index"], px["column_index"]
+        if oi is None or ci is None or len(oi) != len(ci["null_pages"]):
+            return [(0, rows)]
+        if pt == 6:
+            def key(b):
+                return bytes(b)   # Python compares bytes unsigned bytewise, a proper prefix first
+        else:
+            def key(b):
+                return int.from_bytes(b, "little", signed=True)
+        lo = None if lo is None else (bytes(lo) if pt == 6 else int(lo))
+        hi = None if hi is None else (bytes(hi) if pt == 6 else int(hi))
+        out = []
+        for p, (_off, _size, first) in enumerate(oi):
+            if ci["null_pages"][p]:
+                continue
+            if lo is not None and key(ci["max_values"][p]) < lo:
+                continue
+            if hi is not None and key(ci["min_values"][p]) > hi:
+                continue
+            end = oi[p + 1][2] if p + 1 < len(oi) else rows
+            if out and out[-1][1] == first:
+                out[-1] = (out[-1][0], end)
+            else:
+                out.append((first, end))
+        return out
 
     def index_ranges(self, rg, col):
         """((column_index_offset, length) or None, (offset_index_offset, length) or None) of a chunk."""
@@ -210,13 +281,35 @@ class GpuDecoder:
             self._staging = PinnedBuffer(self.h, max(nbytes, 1 << 20))
         return self._staging
 
-    def decode(self, descs, buf_ptr, nbytes, on_device=False):
-        """descs: ChunkDesc list, or a prebuilt ctypes ChunkDesc array (no per-call copy)."""
+    def decode(self, descs, buf_ptr, nbytes, on_device=False, windows=None):
+        """descs: ChunkDesc list, or a prebuilt ctypes ChunkDesc array (no per-call copy). windows: one (skip_rows,
+        take_rows) per chunk (take -1: to the end): the results are cut to those rows on the GPU
+        (pf_decode_row_group_rows); None: pf_decode_row_group."""
         arr = descs if isinstance(descs, C.Array) else (ChunkDesc * max(1, len(descs)))(*descs)
         self._keep = arr
-        check(lib().pf_decode_row_group(self.h, arr, len(descs), C.c_void_p(buf_ptr), nbytes, 1 if on_device else 0),
-              self.h, "pf_decode_row_group")
+        if windows is None:
+            check(lib().pf_decode_row_group(self.h, arr, len(descs), C.c_void_p(buf_ptr), nbytes, 1 if on_device else 0),
+                  self.h, "pf_decode_row_group")
+        else:
+            if len(windows) != len(descs):
+                raise ValueError("one window per chunk")
+            win = (RowWindow * max(1, len(windows)))(*[RowWindow(int(s), int(t)) for s, t in windows])
+            check(lib().pf_decode_row_group_rows(self.h, arr, len(descs), win, C.c_void_p(buf_ptr), nbytes,
+                                                 1 if on_device else 0), self.h, "pf_decode_row_group_rows")
         self.n_chunks = len(descs)
+
+    def window_ms(self):
+        """Time of the window kernels of the last decode (HIP events, ms; 0 without windows or timing)."""
+        return self._debug_window()[0]
+
+    def chars_reruns(self):
+        """How often the last decode's wait ran the batch again because the chars arena overflowed (0 or 1)."""
+        return self._debug_window()[1]
+
+    def _debug_window(self):
+        ms, reruns = C.c_float(), C.c_int()
+        check(lib().pf_debug_window(self.h, C.byref(ms), C.byref(reruns)), self.h, "pf_debug_window")
+        return ms.value, reruns.value
 
     def wait(self):
         return lib().pf_wait(self.h)
@@ -392,13 +485,31 @@ class GpuDecoder:
         return out
 
 
-def decode_file(path, row_groups=None, columns=None, device=0, decoder=None):
-    """Decode the selected chunks of a file on the GPU: {(rg, col): arrays}. One batch."""
+def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, rows=None):
+    """Decode the selected chunks of a file on the GPU: {(rg, col): arrays}. One batch.
+    rows=(lo, hi): rows [lo, hi) of ONE row group (row_groups names it; default 0), counted within it: only the
+    pages its OffsetIndex selects are read and uploaded, and the arrays are cut to the rows on the GPU."""
     with ParquetFile(path) as pf:
         rgs = list(range(pf.num_row_groups)) if row_groups is None else list(row_groups)
         cols = list(range(pf.num_columns)) if columns is None else list(columns)
         dec = decoder or GpuDecoder(device)
         try:
+            if rows is not None:
+                rg = 0 if row_groups is None else rgs[0]
+                if row_groups is not None and len(rgs) != 1:
+                    raise ValueError("rows=(lo, hi) reads one row group")
+                items, total, windows = pf.plan_rows(rg, cols, rows[0], rows[1])
+                buf = dec.staging(total)
+                pf.read_rows(items, buf.ptr.value)
+                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=windows)
+                rc = dec.wait()
+                out = {}
+                for i, (col, *_r) in enumerate(items):
+                    c = pf.columns[col]
+                    out[(rg, col)] = dec.fetch(i, c.physical_type, c.max_def, c.max_rep)
+                out["_status"] = rc
+                out["_error"] = dec.error() if rc else ""
+                return out
             items, total = pf.plan(rgs, cols)
             buf = dec.staging(total)
             descs = []

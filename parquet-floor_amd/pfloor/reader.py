@@ -222,14 +222,21 @@ class RowGroupPipeline:
     chunk bytes of g are read into its context's pinned staging buffer and the decode enqueued
     (pf_decode_row_group is asynchronous); `take(g)` waits for g (pf_wait) and copies its columns
     to the host. A context is reused only after its previous row group was taken, so its staging
-    buffer and output arenas are never overwritten while in use."""
+    buffer and output arenas are never overwritten while in use.
 
-    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2):
+    windows: per entry of row_groups None (the whole row group, the path above) or (lo, hi), rows within that row
+    group: only the pages its OffsetIndex selects are read and uploaded (ParquetFile.plan_rows) and the columns are cut
+    to the rows on the GPU before they cross the link (GpuDecoder.decode(windows=...))."""
+
+    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None):
         if not devices:
             raise ValueError("devices must not be empty")
         self.reader = reader
         self.columns = columns
         self.row_groups = list(row_groups)
+        self.windows = list(windows) if windows is not None else [None] * len(self.row_groups)
+        if len(self.windows) != len(self.row_groups):
+            raise ValueError("one window (or None) per row group")
         self.depth = max(1, int(depth))
         self.decs = []   # [device slot][k]
         self.inflight = collections.OrderedDict()   # position in row_groups -> decoder, or the enqueue error
@@ -254,6 +261,14 @@ class RowGroupPipeline:
         dec = self._decoder(i)
         try:
             idx = [c.index for c in self.columns]
+            if self.windows[i] is not None:
+                lo, hi = self.windows[i]
+                items, total, wins = self.reader.plan_rows(rg, idx, lo, hi)
+                buf = dec.staging(total)
+                self.reader.read_rows(items, buf.ptr.value)
+                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=wins)
+                self.inflight[i] = dec
+                return
             items, total = self.reader.plan([rg], idx)
             buf = dec.staging(total)
             descs = []
@@ -296,14 +311,16 @@ class ParquetReader:
 
     # --- static factories (ParquetReader.java:47-84) ---
     @staticmethod
-    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None):
-        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices))
+    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None):
+        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices, rows))
 
     @staticmethod
-    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None):
-        """devices: GPUs to deal the row groups over (default [device]); rows stay in file order."""
+    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None):
+        """devices: GPUs to deal the row groups over (default [device]); rows stay in file order.
+        rows=(lo, hi): only rows lo .. hi-1 of the file (0 <= lo <= hi <= num_rows): row groups wholly outside are
+        neither read nor decoded, the two edge row groups are read by page and cut on the GPU, inner ones as ever."""
         column_set = frozenset() if columns is None else frozenset(columns)
-        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices)
+        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices, rows)
 
     @staticmethod
     def stream(reader):
@@ -342,7 +359,7 @@ class ParquetReader:
         return f
 
     # --- instance (ParquetReader.java:119-131) ---
-    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None):
+    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None, rows=None):
         try:
             self.reader = ParquetFile(path)
         except Exception as e:
@@ -356,20 +373,40 @@ class ParquetReader:
         self.cursors = None
         self._devices = list(devices) if devices else [device]
         self._pipe = None
+        # the row groups to visit, in order: (row group, None = all of it | (lo, hi) within it)
+        if rows is None:
+            self._visits = [(rg, None) for rg in range(self.reader.num_row_groups)]
+        else:
+            lo, hi = int(rows[0]), int(rows[1])
+            if not 0 <= lo <= hi <= self.reader.num_rows:
+                self.reader.close()
+                raise IllegalArgumentException(f"rows {rows} outside [0, {self.reader.num_rows}]")
+            self._visits = []
+            start = 0
+            for rg in range(self.reader.num_row_groups):
+                n = self.reader.row_group_rows(rg)
+                a, b = max(lo - start, 0), min(hi - start, n)
+                if a < b:
+                    self._visits.append((rg, None if (a, b) == (0, n) else (a, b)))
+                start += n
+        self._pos = -1
 
     def _read_next_row_group(self):
-        self.current_rg += 1
-        if self.current_rg >= self.reader.num_row_groups:
+        self._pos += 1
+        if self._pos >= len(self._visits):
+            self.current_rg = self.reader.num_row_groups
             return False
-        rg = self.current_rg
+        rg, win = self._visits[self._pos]
+        self.current_rg = rg
         if self.reader.row_group_rows(rg) == 0:
             # parquet-mr 1.12.2 ParquetFileReader.readNextRowGroup [upstream, restated]
             raise RuntimeError("Illegal row group of 0 rows")
         if self._pipe is None:
-            self._pipe = RowGroupPipeline(self.reader, self.columns, range(self.reader.num_row_groups), self._devices)
-        arrays = self._pipe.take(rg)
+            self._pipe = RowGroupPipeline(self.reader, self.columns, [v[0] for v in self._visits], self._devices,
+                                          windows=[v[1] for v in self._visits])
+        arrays = self._pipe.take(self._pos)
         self.cursors = [_ColumnCursor(c, a) for c, a in zip(self.columns, arrays)]
-        self.current_row_group_size = self.reader.row_group_rows(rg)
+        self.current_row_group_size = self.reader.row_group_rows(rg) if win is None else win[1] - win[0]
         self.current_row_index = 0
         return True
 
