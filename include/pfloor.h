@@ -206,6 +206,58 @@ typedef struct pf_row_window { int64_t skip_rows; int64_t take_rows; } pf_row_wi
 int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const pf_row_window* windows,
                              const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
 
+/* Filtered decode: a conjunction of simple predicates is evaluated on the GPU over the decoded (and windowed) columns,
+ * and every chunk of the batch is compacted to the matching rows on the device, so only those rows cross the link.
+ * n_preds == 0 is pf_decode_row_group_rows, call for call (no stage, no allocation, batch copies allowed). Otherwise the
+ * row mask is the AND of all predicates, and after pf_wait, pf_column_info_get, pf_copy_column and pf_copy_columns_async
+ * describe every chunk as if it had held only the selected rows, in file order, under the layout rules above:
+ * num_rows = num_entries = num_slots = rows_selected, num_values and num_chars those of the selection, validity from
+ * bit 0 with the unused high bits of the last byte zero, offsets[0] = 0 and only the selected chars, null slots zero
+ * (zero-length for BYTE_ARRAY); rows_selected == 0: empty arrays and offsets = {0}.
+ * A bound is the PLAIN bytes of a value, as Statistics and the ColumnIndex hold them: 4 or 8 little-endian bytes for
+ * INT32 / FLOAT and INT64 / DOUBLE, 1 byte (0 or 1) for BOOLEAN, the raw bytes (at most 4096) for BYTE_ARRAY; a NULL
+ * bound is unbounded. INT32, INT64 and BOOLEAN compare as signed integers; FLOAT and DOUBLE by IEEE lo <= v && v <= hi
+ * (a NaN value or bound matches nothing, -0.0 equals +0.0); BYTE_ARRAY unsigned bytewise, a proper prefix first. A null
+ * row matches only PF_PRED_IS_NULL; a REQUIRED column has no nulls. Unsigned and decimal logical orders are out of
+ * scope: a UINT_* or DECIMAL column is compared by the rules of its physical type.
+ * Call errors (nothing is enqueued): PF_ERR_INVALID_ARG for n_preds outside [0, PF_MAX_PREDICATES], NULL preds with
+ * n_preds > 0, a chunk index out of range, an unknown op, a bound whose length is not the type's width (over 4096 for
+ * BYTE_ARRAY; a BOOLEAN bound other than 0 or 1), a non-NULL bound on IS_NULL / NOT_NULL; PF_ERR_UNSUPPORTED_TYPE for
+ * a predicate on a chunk with max_rep > 0, and for PF_PRED_RANGE on INT96 or FIXED_LEN_BYTE_ARRAY (IS_NULL and NOT_NULL
+ * take any flat type).
+ * Per-chunk status after pf_wait: a predicate chunk that failed to decode or to window gives its status to every chunk
+ * of the batch and to pf_selection_info.status; rows_in is the row count of the first predicate's chunk after its
+ * window, and a chunk whose own count differs gets PF_ERR_INVALID_ARG (a predicate chunk: every chunk does); rows_in
+ * above INT32_MAX is PF_ERR_INVALID_ARG; a payload chunk with max_rep > 0 gets PF_ERR_UNSUPPORTED_TYPE; a payload
+ * chunk's own failure stays its own.
+ * The filter kernels (k_sel_*: pf_filter.hip) write each chunk into the arena that does not hold its input: the twin
+ * arenas of the window stage (allocated for any filtered batch), or back into the decode arenas for a chunk the window
+ * stage moved. After a filtered decode pf_batch_bytes, pf_copy_batch_async and pf_column_info_host return PF_ERR_STATE,
+ * as after a windowed one. */
+#define PF_MAX_PREDICATES 8
+#define PF_PRED_RANGE    0   /* present and lo <= v <= hi; a NULL bound is unbounded; both NULL: every present row */
+#define PF_PRED_IS_NULL  1
+#define PF_PRED_NOT_NULL 2
+typedef struct pf_predicate {
+    int32_t chunk;            /* index into the batch's chunks: the column the predicate reads */
+    int32_t op;               /* PF_PRED_* */
+    const uint8_t* lo; int32_t lo_len;   /* PLAIN bytes of the bound, as Statistics / ColumnIndex hold them */
+    const uint8_t* hi; int32_t hi_len;
+} pf_predicate;
+int pf_decode_row_group_filter(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const pf_row_window* windows,
+                               const pf_predicate* preds, int n_preds, const uint8_t* bytes, size_t n_bytes,
+                               int bytes_on_device);
+typedef struct pf_selection_info {
+    int64_t rows_in;          /* rows the predicates were evaluated over (after the windows) */
+    int64_t rows_selected;
+    const int32_t* d_rows;    /* ascending row numbers, counted from the window's first row; device, ctx-owned */
+    int32_t status;
+} pf_selection_info;
+/* After pf_wait of a filtered decode (PF_ERR_STATE otherwise). */
+int pf_selection_info_get(pf_ctx* ctx, pf_selection_info* out);
+/* The selected row numbers into a host buffer, synchronous; PF_ERR_CAPACITY (nothing copied) below 4 * rows_selected. */
+int pf_copy_selection(pf_ctx* ctx, int32_t* rows, size_t cap_bytes);
+
 /* Block until the enqueued decode has finished; returns the first per-chunk error. */
 int pf_wait(pf_ctx* ctx);
 

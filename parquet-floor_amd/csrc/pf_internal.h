@@ -339,6 +339,39 @@ struct DevWinRes {
     int32_t identity;         // 1: the window keeps every row; nothing was copied, the decode arenas hold the result
 };
 
+// Row filters (pf_filter.hip, pf_decode_row_group_filter): the predicates as plan_filter packs them, each chunk's input
+// and output arrays as k_sel_prep resolves them on the device (the input lies where the window stage left it; the output
+// goes to the arena that does not hold the input), and the stage's head. Tiles are SEL_TILE rows: 16 mask words.
+constexpr uint32_t SEL_TILE = 1024;          // rows per workgroup round of the k_sel_* kernels (a multiple of 256)
+constexpr uint32_t SEL_LONG = 32;            // BYTE_ARRAY values longer than this are copied by a whole wave
+constexpr int32_t PRED_HAS_LO = 1, PRED_HAS_HI = 2;
+constexpr int32_t PRED_BOUND_MAX = 4096;     // bytes of a BYTE_ARRAY bound
+struct DevPred {
+    int32_t chunk, op, ptype, flags;   // op: PF_PRED_*; flags: PRED_HAS_*
+    int64_t lo_i, hi_i;                // INT32, INT64, BOOLEAN
+    double lo_f, hi_f;                 // FLOAT (widened), DOUBLE
+    uint32_t lo_off, lo_len, hi_off, hi_len;   // BYTE_ARRAY: the bounds in the blob behind the table
+};
+struct DevSelChunk {
+    const uint8_t* values;    // input
+    const uint8_t* validity;
+    const int32_t* offsets;
+    const uint8_t* chars;
+    uint8_t* o_values;        // output
+    uint8_t* o_validity;
+    int32_t* o_offsets;
+    uint8_t* o_chars;
+    int64_t n_rows;           // rows of the input (after its window)
+    int64_t n_values, n_chars;   // of the selection (k_sel_fin)
+    int32_t width, ptype, max_def;
+    int32_t status;           // the chunk's status after the filter
+};
+struct DevSelHead {
+    int64_t rows_in, rows_selected;
+    int32_t status;           // a predicate chunk's failure (every chunk takes it), or rows_in out of range
+    int32_t pad;
+};
+
 // GPU page-header scan (pf_scan.hip, pf_scan_pages)
 struct ScanChunk {            // device copy of pf_scan_chunk
     const uint8_t* base;      // chunk's first byte

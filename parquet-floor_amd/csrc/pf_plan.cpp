@@ -559,4 +559,77 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
     }
 }
 
+// ---- row filters ---------------------------------------------------------------------------------------------------
+
+int plan_filter(const pf_chunk_desc* cds, int n_chunks, const pf_predicate* preds, int n_preds, FilterPlan& f, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    f.preds.clear();
+    f.blob.clear();
+    auto bad = [&](int code, const char* text) {
+        f.preds.clear();
+        f.blob.clear();
+        *why = text;
+        return code;
+    };
+    if (n_preds < 0 || n_preds > PF_MAX_PREDICATES) return bad(PF_ERR_INVALID_ARG, "predicates: n_preds outside [0, PF_MAX_PREDICATES]");
+    if (n_preds > 0 && (!preds || !cds)) return bad(PF_ERR_INVALID_ARG, "predicates: null table");
+    for (int i = 0; i < n_preds; i++) {
+        const pf_predicate& q = preds[i];
+        if (q.chunk < 0 || q.chunk >= n_chunks) return bad(PF_ERR_INVALID_ARG, "predicate: chunk index out of range");
+        if (q.op != PF_PRED_RANGE && q.op != PF_PRED_IS_NULL && q.op != PF_PRED_NOT_NULL) return bad(PF_ERR_INVALID_ARG, "predicate: unknown op");
+        const pf_chunk_desc& cd = cds[q.chunk];
+        if (q.op != PF_PRED_RANGE && (q.lo || q.hi)) return bad(PF_ERR_INVALID_ARG, "predicate: IS_NULL / NOT_NULL take no bound");
+        if (cd.max_rep > 0) return bad(PF_ERR_UNSUPPORTED_TYPE, "predicate: a column with repetition");
+        DevPred d{};
+        d.chunk = q.chunk;
+        d.op = q.op;
+        d.ptype = cd.physical_type;
+        if (q.op == PF_PRED_RANGE) {
+            const int pt = cd.physical_type;
+            if (pt != PF_BOOLEAN && pt != PF_INT32 && pt != PF_INT64 && pt != PF_FLOAT && pt != PF_DOUBLE && pt != PF_BYTE_ARRAY)
+                return bad(PF_ERR_UNSUPPORTED_TYPE, "predicate: a range over INT96, FIXED_LEN_BYTE_ARRAY or an unknown type");
+            for (int side = 0; side < 2; side++) {
+                const uint8_t* b = side ? q.hi : q.lo;
+                const int32_t n = side ? q.hi_len : q.lo_len;
+                if (!b) continue;
+                d.flags |= side ? PRED_HAS_HI : PRED_HAS_LO;
+                if (pt == PF_BYTE_ARRAY) {
+                    if (n < 0 || n > PRED_BOUND_MAX) return bad(PF_ERR_INVALID_ARG, "predicate: a BYTE_ARRAY bound of more than 4096 bytes");
+                    (side ? d.hi_off : d.lo_off) = uint32_t(f.blob.size());
+                    (side ? d.hi_len : d.lo_len) = uint32_t(n);
+                    f.blob.insert(f.blob.end(), b, b + n);
+                    continue;
+                }
+                if (n != type_width(pt, 0)) return bad(PF_ERR_INVALID_ARG, "predicate: a bound whose length is not the type's width");
+                uint64_t raw = 0;
+                for (int k = 0; k < n; k++) raw |= uint64_t(b[k]) << (8 * k);   // little-endian
+                int64_t iv = 0;
+                double fv = 0;
+                if (pt == PF_BOOLEAN) {
+                    if (raw > 1) return bad(PF_ERR_INVALID_ARG, "predicate: a BOOLEAN bound is the byte 0 or 1");
+                    iv = int64_t(raw);
+                } else if (pt == PF_INT32) {
+                    iv = int64_t(int32_t(uint32_t(raw)));
+                } else if (pt == PF_INT64) {
+                    iv = int64_t(raw);
+                } else if (pt == PF_FLOAT) {
+                    const uint32_t w = uint32_t(raw);
+                    float x;
+                    static_assert(sizeof x == sizeof w, "float is 32 bits");
+                    __builtin_memcpy(&x, &w, 4);
+                    fv = double(x);
+                } else {
+                    __builtin_memcpy(&fv, &raw, 8);
+                }
+                (side ? d.hi_i : d.lo_i) = iv;
+                (side ? d.hi_f : d.lo_f) = fv;
+            }
+        }
+        f.preds.push_back(d);
+    }
+    *why = "";
+    return PF_OK;
+}
+
 }  // namespace pf

@@ -120,4 +120,13 @@ struct BatchPlan {
 void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const PfOpts& opts, BatchPlan& p);
 void bind_batch(BatchPlan& p, const ArenaBases& a);
 
+// The predicates of a filtered decode, validated and packed for the device: the DevPred table and, behind it, the
+// blob that holds the BYTE_ARRAY bounds (DevPred.lo_off / hi_off). Reads the descriptors and the bounds, nothing else.
+struct FilterPlan {
+    std::vector<DevPred> preds;
+    std::vector<uint8_t> blob;
+};
+// PF_OK, or the call error of pf_decode_row_group_filter with its text in *why (f is then empty).
+int plan_filter(const pf_chunk_desc* cds, int n_chunks, const pf_predicate* preds, int n_preds, FilterPlan& f, const char** why);
+
 }  // namespace pf

@@ -204,6 +204,18 @@ struct pf_ctx {
     HostBuf h_win;                         // DevWin[n] up, DevWinRes[n] down
     int win_grid = 1;
     hipEvent_t ev_win[2] = {};
+    // row filter (pf_decode_row_group_filter): the packed predicates (none: no filter stage), the stage's device buffer
+    // and its pinned mirror: [DevSelHead | DevSelChunk[n]] comes down, [DevPred[] | blob | win_of[n]] goes up
+    pf::FilterPlan filt;
+    DevBuf d_sel;
+    HostBuf h_sel;
+    pf::SelBufs sel{};
+    size_t sel_up_off = 0;                 // where the uploaded tables begin: the bytes before them come down
+    int sel_grid = 1;
+    hipEvent_t ev_sel[2] = {};
+    pf_selection_info sel_info{};
+    bool filtered() const { return !filt.preds.empty(); }
+    bool twins() const { return !wins.empty() || filtered(); }   // the batch's results are not (all) in the decode arenas
 };
 
 namespace {
@@ -324,6 +336,17 @@ int enqueue_kernels(pf_ctx* ctx) {
         EVREC(ctx, ctx->ev_win[1], st);
         HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_win.p) + res_off, d_wres, sizeof(DevWinRes) * nw,
                                    hipMemcpyDeviceToHost, st));
+    }
+    if (ctx->filtered()) {   // the row filter: after the windows, so it sees their rows and a chars rerun filters again
+        const DevWinRes* d_wres = ctx->wins.empty() ? nullptr : reinterpret_cast<const DevWinRes*>(
+            static_cast<const uint8_t*>(ctx->d_win.p) + align_up(sizeof(DevWin) * ctx->wins.size(), 256));
+        EVREC(ctx, ctx->ev_sel[0], st);
+        launch_filter(d_chunks, d_res, d_wres, ctx->sel, ctx->n_chunks, ctx->sel_grid, static_cast<const uint8_t*>(ctx->d_chars.p),
+                      static_cast<uint8_t*>(ctx->d_wchars.p),
+                      static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p),
+                      static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p), st);
+        EVREC(ctx, ctx->ev_sel[1], st);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_sel.p, ctx->d_sel.p, ctx->sel_up_off, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipGetLastError());
     // results + device-written chunk fields (chars base) back to pinned host memory
@@ -1335,6 +1358,7 @@ int ctx_init(pf_ctx* ctx, pf_ctx* peer) {
     for (auto& e : ctx->ev) HIPCHK(nullptr, hipEventCreate(&e));
     for (auto& e : ctx->ev_bloom) HIPCHK(nullptr, hipEventCreate(&e));
     for (auto& e : ctx->ev_win) HIPCHK(nullptr, hipEventCreate(&e));
+    for (auto& e : ctx->ev_sel) HIPCHK(nullptr, hipEventCreate(&e));
     return PF_OK;
 }
 
@@ -1383,9 +1407,10 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     if (ctx->copies_pending) (void)hipEventSynchronize(ctx->ev_copy);   // (a download on the copy stream)
     for (DevBuf* b : {&ctx->d_in, &ctx->d_scratch, &ctx->d_out, &ctx->d_bits, &ctx->d_chars, &ctx->d_meta, &ctx->d_tokmap,
                       &ctx->d_scan_in, &ctx->d_scan, &ctx->d_enc, &ctx->d_enc_sec, &ctx->d_enc_out, &ctx->d_win, &ctx->d_wout,
-                      &ctx->d_wbits, &ctx->d_wchars})
+                      &ctx->d_wbits, &ctx->d_wchars, &ctx->d_sel})
         b->release();
     ctx->h_win.release();
+    ctx->h_sel.release();
     ctx->h_meta.release();
     ctx->h_res.release();
     ctx->h_enc_slots.release();
@@ -1395,6 +1420,7 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_bloom) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_win) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->ev_sel) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
     if (ctx->ev_dl) (void)hipEventDestroy(ctx->ev_dl);
@@ -1436,10 +1462,62 @@ int pf_memcpy_h2d(pf_ctx* ctx, void* dst, const void* src, size_t bytes) {
 }  // extern "C"
 
 namespace {
+// The filter stage's buffer for the planned batch: sized from the host's row counts, its tables uploaded.
+int bind_filter(pf_ctx* ctx) {
+    const BatchPlan& p = ctx->plan;
+    const FilterPlan& f = ctx->filt;
+    const size_t nc = size_t(ctx->n_chunks), np = f.preds.size();
+    std::vector<int32_t> win_of(nc, -1);
+    for (size_t i = 0; i < ctx->wins.size(); i++) win_of[size_t(ctx->wins[i].chunk)] = int32_t(i);
+    // rows_in is the first predicate chunk's row count after its window: at most take rows, or the chunk's entries
+    // (a predicate chunk is flat: rows = entries)
+    const int c0 = f.preds[0].chunk;
+    int64_t rows_cap = p.chunks[size_t(c0)].num_entries;
+    if (win_of[size_t(c0)] >= 0 && ctx->wins[size_t(win_of[size_t(c0)])].take >= 0)
+        rows_cap = std::min<int64_t>(rows_cap, ctx->wins[size_t(win_of[size_t(c0)])].take);
+    rows_cap = std::max<int64_t>(rows_cap, 0);
+    const size_t tiles = std::max<size_t>(1, (size_t(rows_cap) + SEL_TILE - 1) / SEL_TILE);
+    size_t m = 0;
+    auto take = [&](size_t n) { const size_t o = align_up(m, 256); m = o + n; return o; };
+    const size_t o_head = take(sizeof(DevSelHead)), o_sc = take(sizeof(DevSelChunk) * nc);
+    const size_t o_up = take(0), o_preds = take(sizeof(DevPred) * np), o_blob = take(f.blob.size()), o_winof = take(4 * nc);
+    const size_t up_end = m;
+    const size_t o_mask = take(8 * tiles * (SEL_TILE / 64)), o_tc = take(4 * tiles), o_tb = take(4 * tiles);
+    const size_t o_rows = take(4 * tiles * SEL_TILE), o_bs = take(4 * tiles * nc), o_bb = take(4 * tiles * nc), o_bt = take(8 * nc);
+    HIPCHK(ctx, ctx->d_sel.ensure(m));
+    HIPCHK(ctx, ctx->h_sel.ensure(up_end));
+    uint8_t* h = static_cast<uint8_t*>(ctx->h_sel.p);
+    uint8_t* d = static_cast<uint8_t*>(ctx->d_sel.p);
+    std::memset(h, 0, up_end);
+    std::memcpy(h + o_preds, f.preds.data(), sizeof(DevPred) * np);
+    if (!f.blob.empty()) std::memcpy(h + o_blob, f.blob.data(), f.blob.size());
+    std::memcpy(h + o_winof, win_of.data(), 4 * nc);
+    HIPCHK(ctx, hipMemcpyAsync(d + o_up, h + o_up, up_end - o_up, hipMemcpyHostToDevice, ctx->stream));
+    SelBufs& s = ctx->sel;
+    s.head = reinterpret_cast<DevSelHead*>(d + o_head);
+    s.sc = reinterpret_cast<DevSelChunk*>(d + o_sc);
+    s.preds = reinterpret_cast<const DevPred*>(d + o_preds);
+    s.blob = d + o_blob;
+    s.win_of = reinterpret_cast<const int32_t*>(d + o_winof);
+    s.mask = reinterpret_cast<uint64_t*>(d + o_mask);
+    s.tile_count = reinterpret_cast<uint32_t*>(d + o_tc);
+    s.tile_base = reinterpret_cast<uint32_t*>(d + o_tb);
+    s.rows = reinterpret_cast<int32_t*>(d + o_rows);
+    s.ba_sum = reinterpret_cast<uint32_t*>(d + o_bs);
+    s.ba_base = reinterpret_cast<uint32_t*>(d + o_bb);
+    s.ba_total = reinterpret_cast<int64_t*>(d + o_bt);
+    s.rows_cap = rows_cap;
+    s.tiles_cap = int64_t(tiles);
+    s.n_preds = int32_t(np);
+    ctx->sel_up_off = o_up;
+    ctx->sel_grid = int(std::min<size_t>(tiles, 256));
+    return PF_OK;
+}
+
 // Plan, upload and enqueue one batch; ctx->wins lists the chunks to be windowed.
 int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
                   int bytes_on_device) {
-    const bool windowed = !ctx->wins.empty();
+    const bool windowed = !ctx->wins.empty(), twins = ctx->twins();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // diagnostics: PF_DEBUG_PLAN=1 prints the host time of each phase (microseconds)
@@ -1470,10 +1548,10 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     // ---- arenas ----
     const size_t chars_cap = std::max<size_t>(size_t(2 * p.chars_hint) + (16u << 20), ctx->chars_need);
     // (the window kernels read validity bits in 8-byte words: room for the last one)
-    const size_t bits_cap = std::max<size_t>(p.bits_bytes, 1) + (windowed ? 8 : 0);
+    const size_t bits_cap = std::max<size_t>(p.bits_bytes, 1) + (twins ? 8 : 0);
     if (ctx->copies_pending) {
         if (p.out_bytes > ctx->d_out.cap || bits_cap > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap ||
-            (windowed && (ctx->d_out.cap > ctx->d_wout.cap || ctx->d_bits.cap > ctx->d_wbits.cap || ctx->d_chars.cap > ctx->d_wchars.cap)))
+            (twins && (ctx->d_out.cap > ctx->d_wout.cap || ctx->d_bits.cap > ctx->d_wbits.cap || ctx->d_chars.cap > ctx->d_wchars.cap)))
             HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // a growing output arena must not be freed under a pending D2H copy
         else
             HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_copy, 0));   // (a download on the copy stream reads the arenas)
@@ -1483,12 +1561,14 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(p.out_bytes, 1)));
     HIPCHK(ctx, ctx->d_bits.ensure(bits_cap));
     HIPCHK(ctx, ctx->d_chars.ensure(chars_cap));
-    if (windowed) {   // the twins: the decode arenas' sizes, so a chunk keeps its offsets
-        const int nw = int(ctx->wins.size());
-        const size_t tab = align_up(sizeof(DevWin) * nw, 256) + sizeof(DevWinRes) * nw;
+    if (twins) {   // the twins: the decode arenas' sizes, so a chunk keeps its offsets
         HIPCHK(ctx, ctx->d_wout.ensure(ctx->d_out.cap));
         HIPCHK(ctx, ctx->d_wbits.ensure(ctx->d_bits.cap));
         HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
+    }
+    if (windowed) {
+        const int nw = int(ctx->wins.size());
+        const size_t tab = align_up(sizeof(DevWin) * nw, 256) + sizeof(DevWinRes) * nw;
         HIPCHK(ctx, ctx->d_win.ensure(tab));
         HIPCHK(ctx, ctx->h_win.ensure(tab));
         std::memcpy(ctx->h_win.p, ctx->wins.data(), sizeof(DevWin) * nw);
@@ -1500,6 +1580,10 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
             tiles = std::max<uint64_t>(tiles, n * uint64_t(std::max(ck.width, 8)) / WIN_TILE + 8);
         }
         ctx->win_grid = int(std::min<uint64_t>(tiles, 512));
+    }
+    if (ctx->filtered()) {
+        const int rc = bind_filter(ctx);
+        if (rc) return rc;
     }
     HIPCHK(ctx, ctx->d_tokmap.ensure(p.snap.tokmap_bytes));
     HIPCHK(ctx, ctx->d_meta.ensure(p.meta_bytes));
@@ -1528,9 +1612,9 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     return PF_OK;
 }
 
-// pf_decode_row_group (windows == nullptr) and pf_decode_row_group_rows.
-int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows, const uint8_t* bytes,
-                 size_t n_bytes, int bytes_on_device) {
+// pf_decode_row_group (windows == nullptr), pf_decode_row_group_rows and pf_decode_row_group_filter (n_preds > 0).
+int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows, const pf_predicate* preds,
+                 int n_preds, const uint8_t* bytes, size_t n_bytes, int bytes_on_device) {
     if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
     if (n_chunks < 0 || (n_chunks > 0 && (!cds || !bytes))) return fail(ctx, PF_ERR_INVALID_ARG, "bad arguments");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
@@ -1538,11 +1622,22 @@ int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_r
         if (windows[c].skip_rows < 0 || windows[c].take_rows < -1)
             return fail(ctx, PF_ERR_INVALID_ARG, "row window: negative skip_rows, or take_rows below -1");
     ctx->wins.clear();
+    ctx->filt.preds.clear();
+    ctx->filt.blob.clear();
+    if (n_preds != 0) {   // (a predicate error leaves the lists cleared, like an enqueue error below)
+        const char* why = "";
+        const int rc = plan_filter(cds, n_chunks, preds, n_preds, ctx->filt, &why);
+        if (rc) return fail(ctx, rc, why);
+    }
     for (int c = 0; windows && c < n_chunks; c++)
         if (windows[c].skip_rows != 0 || windows[c].take_rows != -1)
             ctx->wins.push_back(DevWin{c, 0, windows[c].skip_rows, windows[c].take_rows});
     const int rc = enqueue_batch(ctx, cds, n_chunks, bytes, n_bytes, bytes_on_device);
-    if (rc) ctx->wins.clear();   // nothing windowed is pending: the batch-copy gates must not answer for this call
+    if (rc) {   // nothing windowed or filtered is pending: the batch-copy gates must not answer for this call
+        ctx->wins.clear();
+        ctx->filt.preds.clear();
+        ctx->filt.blob.clear();
+    }
     return rc;
 }
 }  // namespace
@@ -1551,12 +1646,50 @@ extern "C" {
 
 int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
                         int bytes_on_device) {
-    return decode_batch(ctx, cds, n_chunks, nullptr, bytes, n_bytes, bytes_on_device);
+    return decode_batch(ctx, cds, n_chunks, nullptr, nullptr, 0, bytes, n_bytes, bytes_on_device);
 }
 
 int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows,
                              const uint8_t* bytes, size_t n_bytes, int bytes_on_device) {
-    return decode_batch(ctx, cds, n_chunks, windows, bytes, n_bytes, bytes_on_device);
+    return decode_batch(ctx, cds, n_chunks, windows, nullptr, 0, bytes, n_bytes, bytes_on_device);
+}
+
+int pf_decode_row_group_filter(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows,
+                               const pf_predicate* preds, int n_preds, const uint8_t* bytes, size_t n_bytes, int bytes_on_device) {
+    return decode_batch(ctx, cds, n_chunks, windows, preds, n_preds, bytes, n_bytes, bytes_on_device);
+}
+
+int pf_selection_info_get(pf_ctx* ctx, pf_selection_info* out) {
+    if (!ctx || !out) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    if (!ctx->tables_from_decode || !ctx->filtered()) return fail(ctx, PF_ERR_STATE, "the last decode had no row filter");
+    *out = ctx->sel_info;
+    return PF_OK;
+}
+
+int pf_copy_selection(pf_ctx* ctx, int32_t* rows, size_t cap_bytes) {
+    if (!ctx || (!rows && cap_bytes)) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    if (!ctx->tables_from_decode || !ctx->filtered()) return fail(ctx, PF_ERR_STATE, "the last decode had no row filter");
+    const size_t n = 4 * size_t(ctx->sel_info.rows_selected);
+    if (n > cap_bytes) return fail(ctx, PF_ERR_CAPACITY, "selection buffer too small");
+    if (!n) return PF_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(rows, ctx->sel_info.d_rows, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_copy, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
+    return PF_OK;
+}
+
+// Diagnostics (not part of pfloor.h): the filter stage of the last finished decode. *ms: time of its kernels (HIP events;
+// 0 when the decode had no predicates or stage timing is off; not a stage of pf_last_timing).
+int pf_debug_filter(pf_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    *ms = 0;
+    if (!ctx->timing_valid || !ctx->timing || !ctx->filtered()) return PF_OK;
+    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev_sel[0], ctx->ev_sel[1]));
+    return PF_OK;
 }
 
 // Diagnostics (not part of pfloor.h): the window stage of the last finished decode. *ms: time of its kernels (HIP
@@ -1594,7 +1727,7 @@ int pf_wait(pf_ctx* ctx) {
             ctx->reruns++;
             ctx->chars_need = size_t(need) + (1u << 20);
             HIPCHK(ctx, ctx->d_chars.ensure(ctx->chars_need));
-            if (!ctx->wins.empty()) HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
+            if (ctx->twins()) HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
             int rc = upload_meta(ctx);
             if (rc) { ctx->pending = false; return rc; }
             rc = enqueue_kernels(ctx);
@@ -1643,6 +1776,28 @@ int pf_wait(pf_ctx* ctx) {
                     ci.d_list_validity = tw(ck.list_validity, bd);
                     ci.d_def_levels = tw(ck.def_levels, od);
                     ci.d_rep_levels = tw(ck.rep_levels, od);
+                }
+            }
+            if (ctx->filtered()) {   // the selection's view
+                const DevSelHead& sh = *static_cast<const DevSelHead*>(ctx->h_sel.p);
+                const DevSelChunk& sc = reinterpret_cast<const DevSelChunk*>(static_cast<const uint8_t*>(ctx->h_sel.p) +
+                                                                            align_up(sizeof(DevSelHead), 256))[c];
+                if (ci.status == 0 && sc.status != 0) ci.status = sc.status;   // (its own, or a predicate chunk's)
+                else if (ci.status == 0) {
+                    ci.num_entries = ci.num_slots = ci.num_rows = sh.rows_selected;
+                    ci.num_values = sc.n_values;
+                    ci.num_chars = ck.ptype == PF_BYTE_ARRAY ? sc.n_chars : 0;
+                    ci.d_values = sc.o_values;
+                    ci.d_validity = sc.o_validity;
+                    ci.d_offsets = sc.o_offsets;
+                    ci.d_chars = sc.o_chars;
+                }
+                if (c == 0) {
+                    ctx->sel_info = pf_selection_info{};
+                    ctx->sel_info.rows_in = sh.rows_in;
+                    ctx->sel_info.rows_selected = sh.rows_selected;
+                    ctx->sel_info.d_rows = ctx->sel.rows;
+                    ctx->sel_info.status = sh.status;
                 }
             }
             if (ci.status != 0 && first_err == PF_OK) {
@@ -1764,7 +1919,7 @@ int pf_batch_bytes(pf_ctx* ctx, size_t* bytes) {
     if (!ctx || !bytes) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
-    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
+    if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
     *bytes = batch_layout(ctx).total;
     return PF_OK;
 }
@@ -1773,7 +1928,7 @@ int pf_copy_batch_async(pf_ctx* ctx, void* host, size_t cap) {
     if (!ctx || (!host && cap)) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
-    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
+    if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
     const BatchLayout b = batch_layout(ctx);
     if (b.total > cap) return fail(ctx, PF_ERR_CAPACITY, "batch buffer too small (pf_batch_bytes)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1823,7 +1978,7 @@ int pf_column_info_host(pf_ctx* ctx, int chunk, const void* host, pf_column_info
     if (!ctx || !out || !host) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
-    if (!ctx->wins.empty()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows: no batch copy");
+    if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
     const BatchLayout b = batch_layout(ctx);
     const uint8_t* h = static_cast<const uint8_t*>(host);
     auto rebase = [&](const void* p) -> const void* {

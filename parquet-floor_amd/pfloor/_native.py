@@ -94,6 +94,19 @@ class RowWindow(C.Structure):
     _fields_ = [("skip_rows", C.c_int64), ("take_rows", C.c_int64)]
 
 
+PF_MAX_PREDICATES = 8
+PRED_RANGE, PRED_IS_NULL, PRED_NOT_NULL = 0, 1, 2
+
+
+class Predicate(C.Structure):
+    _fields_ = [("chunk", C.c_int32), ("op", C.c_int32), ("lo", C.c_void_p), ("lo_len", C.c_int32),
+                ("hi", C.c_void_p), ("hi_len", C.c_int32)]
+
+
+class SelectionInfo(C.Structure):
+    _fields_ = [("rows_in", C.c_int64), ("rows_selected", C.c_int64), ("d_rows", C.c_void_p), ("status", C.c_int32)]
+
+
 class PfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -150,6 +163,11 @@ def _load(path):
         "pf_decode_row_group": ([vp, C.POINTER(ChunkDesc), i32, vp, sz, i32], C.c_int),
         "pf_decode_row_group_rows": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), vp, sz, i32], C.c_int),
         "pf_debug_window": ([vp, C.POINTER(C.c_float), C.POINTER(C.c_int)], C.c_int),   # (diagnostics, not in pfloor.h)
+        "pf_decode_row_group_filter": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), C.POINTER(Predicate), i32, vp, sz,
+                                        i32], C.c_int),
+        "pf_selection_info_get": ([vp, C.POINTER(SelectionInfo)], C.c_int),
+        "pf_copy_selection": ([vp, vp, sz], C.c_int),
+        "pf_debug_filter": ([vp, C.POINTER(C.c_float)], C.c_int),   # (diagnostics, not in pfloor.h)
         "pf_wait": ([vp], C.c_int),
         "pf_column_info_get": ([vp, i32, C.POINTER(ColumnInfo)], C.c_int),
         "pf_copy_column": ([vp, i32, C.POINTER(ColumnOut)], C.c_int),

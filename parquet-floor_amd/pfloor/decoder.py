@@ -4,11 +4,12 @@
 :183); `GpuDecoder` owns one pf_ctx (one GPU, one HIP stream) and turns column chunks into
 decoded columnar numpy arrays in the canonical layout of include/pfloor.h."""
 import ctypes as C
+import os
 
 import numpy as np
 
 from ._native import (ChunkDesc, ChunkRows, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, PageLocation,
-                      RowWindow, ScanChunk, ScanResult, check, lib)
+                      Predicate, RowWindow, ScanChunk, ScanResult, SelectionInfo, check, lib)
 
 CONVERTED_UTF8, CONVERTED_ENUM, CONVERTED_JSON = 0, 4, 19
 LOGICAL_STRING, LOGICAL_ENUM, LOGICAL_JSON = 1, 4, 12
@@ -48,6 +49,65 @@ class ColumnDescriptor:
 
     def __repr__(self):
         return f"ColumnDescriptor({'.'.join(self.path)}, type={self.physical_type}, def={self.max_def}, rep={self.max_rep})"
+
+
+def _bloom_header(raw):
+    """(numBytes, the header's length) of a Thrift compact BloomFilterHeader {1: i32 numBytes, 2: algorithm, 3: hash,
+    4: compression} (the three unions hold one empty struct each); unknown fields are skipped."""
+    pos = 0
+
+    def varint():
+        nonlocal pos
+        v = shift = 0
+        while True:
+            if pos >= len(raw) or shift > 63:
+                raise ValueError("BloomFilterHeader: truncated")
+            b = raw[pos]
+            pos += 1
+            v |= (b & 0x7f) << shift
+            shift += 7
+            if not b & 0x80:
+                return v
+
+    def skip(t):
+        nonlocal pos
+        if t in (1, 2):
+            return
+        if t == 3:
+            pos += 1
+        elif t in (4, 5, 6):
+            varint()
+        elif t == 7:
+            pos += 8
+        elif t == 8:
+            pos += varint()
+        elif t == 12:
+            struct(None)
+        else:
+            raise ValueError(f"BloomFilterHeader: unexpected Thrift type {t}")
+
+    def struct(out):
+        nonlocal pos
+        fid = 0
+        while True:
+            if pos >= len(raw):
+                raise ValueError("BloomFilterHeader: truncated")
+            b = raw[pos]
+            pos += 1
+            if b == 0:
+                return
+            t = b & 0x0f
+            fid = fid + (b >> 4) if b >> 4 else ((lambda z: (z >> 1) ^ -(z & 1))(varint()))
+            if out is not None and fid == 1 and t == 5:
+                z = varint()
+                out.append((z >> 1) ^ -(z & 1))
+            else:
+                skip(t)
+    found = []
+    struct(found)
+    if not found or found[0] <= 0:
+        raise ValueError("BloomFilterHeader: no numBytes")
+    return found[0], pos
 
 
 class ParquetFile:
@@ -168,6 +228,64 @@ class ParquetFile:
                 out.append((first, end))
         return out
 
+    def bloom_probe(self, rg, col, plain_bytes):
+        """True: the value (its PLAIN bytes; BYTE_ARRAY without the length prefix) may be in the chunk; False: it is
+        not; None: the chunk has no Bloom filter. Host only: pf_file_chunk_bloom, pf_file_read, pf_xxh64 and
+        pf_bloom_check; the BloomFilterHeader is read for numBytes (and for its own length when the footer gives none)."""
+        L = lib()
+        off, length = C.c_int64(), C.c_int32()
+        check(L.pf_file_chunk_bloom(self.h, rg, col, C.byref(off), C.byref(length)), None, f"bloom rg{rg} c{col}")
+        if off.value < 0:
+            return None
+        head = (C.c_uint8 * 64)()
+        file_size = os.path.getsize(self.path)
+        n_head = min(64, file_size - off.value)
+        self.read_into(off.value, n_head, C.addressof(head))
+        num_bytes, header_len = _bloom_header(bytes(head[:n_head]))
+        start = off.value + (length.value - num_bytes if length.value >= 0 else header_len)
+        bits = (C.c_uint8 * max(1, num_bytes))()
+        self.read_into(start, num_bytes, C.addressof(bits))
+        self.bloom_bytes_read = getattr(self, "bloom_bytes_read", 0) + n_head + num_bytes
+        raw = bytes(plain_bytes)
+        buf = C.create_string_buffer(raw, max(1, len(raw)))
+        rc = L.pf_bloom_check(bits, num_bytes, L.pf_xxh64(buf, len(raw), 0))
+        if rc < 0:
+            check(rc, None, f"bloom rg{rg} c{col}: a bitset of {num_bytes} bytes")
+        return bool(rc)
+
+    def prune_row_group(self, rg, preds, lo=0, hi=None):
+        """What of rows [lo, hi) of a row group a conjunction of pfloor.predicate predicates can match, from the page
+        index and the Bloom filters alone: None to skip the row group, or (row_lo, row_hi). Every Range / Eq on an INT32,
+        INT64 or BYTE_ARRAY column contributes the hull of candidate_rows (no candidate page: skip); every Eq on a chunk
+        with a Bloom filter is probed (a negative probe: skip); everything else leaves the range whole."""
+        return self._prune(rg, preds, lo, hi)[0]
+
+    def _prune(self, rg, preds, lo=0, hi=None):
+        """(prune_row_group's result, "index" | "bloom" | None: what skipped the row group)."""
+        from .predicate import Eq, Range, resolve
+        hi = self.row_group_rows(rg) if hi is None else hi
+        bound = []
+        for p in preds:
+            if isinstance(p, Range):
+                col = resolve(self.columns, p.column)
+                pt = self.columns[col].physical_type
+                if pt in (1, 2, 6):
+                    a, b = p.bounds(pt)
+                    bound.append((p, col, pt, a, b))
+        for p, col, pt, a, b in bound:
+            def value(x):
+                return None if x is None else (x if pt == 6 else int.from_bytes(x, "little", signed=True))
+            cand = self.candidate_rows(rg, col, value(a), value(b))
+            if not cand:
+                return None, "index"
+            lo, hi = max(lo, cand[0][0]), min(hi, cand[-1][1])
+            if lo >= hi:
+                return None, "index"
+        for p, col, pt, a, b in bound:
+            if isinstance(p, Eq) and self.bloom_probe(rg, col, a) is False:
+                return None, "bloom"
+        return (lo, hi), None
+
     def index_ranges(self, rg, col):
         """((column_index_offset, length) or None, (offset_index_offset, length) or None) of a chunk."""
         co, oo, cl, ol = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
@@ -281,13 +399,32 @@ class GpuDecoder:
             self._staging = PinnedBuffer(self.h, max(nbytes, 1 << 20))
         return self._staging
 
-    def decode(self, descs, buf_ptr, nbytes, on_device=False, windows=None):
+    def decode(self, descs, buf_ptr, nbytes, on_device=False, windows=None, predicates=None):
         """descs: ChunkDesc list, or a prebuilt ctypes ChunkDesc array (no per-call copy). windows: one (skip_rows,
         take_rows) per chunk (take -1: to the end): the results are cut to those rows on the GPU
-        (pf_decode_row_group_rows); None: pf_decode_row_group."""
+        (pf_decode_row_group_rows); None: pf_decode_row_group. predicates: a list of (chunk, op, lo, hi) -- chunk an
+        index into descs, op a PF_PRED_* code, lo / hi the PLAIN bytes of a bound or None (pfloor.predicate.bind makes
+        them): a conjunction evaluated on the GPU, every chunk compacted to the matching rows
+        (pf_decode_row_group_filter; selection() has the row numbers). None: no filter."""
         arr = descs if isinstance(descs, C.Array) else (ChunkDesc * max(1, len(descs)))(*descs)
         self._keep = arr
-        if windows is None:
+        if predicates is not None:
+            if windows is not None and len(windows) != len(descs):
+                raise ValueError("one window per chunk")
+            win = None if windows is None else (RowWindow * max(1, len(windows)))(*[RowWindow(int(s), int(t)) for s, t in windows])
+            preds = (Predicate * max(1, len(predicates)))()
+            keep = []   # the bounds' buffers, alive over the call (the library copies them before it returns)
+            for i, (chunk, op, lo, hi) in enumerate(predicates):
+                preds[i].chunk, preds[i].op = int(chunk), int(op)
+                for side, b in (("lo", lo), ("hi", hi)):
+                    if b is not None:
+                        raw = C.create_string_buffer(bytes(b), max(1, len(b)))
+                        keep.append(raw)
+                        setattr(preds[i], side, C.addressof(raw))
+                        setattr(preds[i], side + "_len", len(b))
+            check(lib().pf_decode_row_group_filter(self.h, arr, len(descs), win, preds, len(predicates), C.c_void_p(buf_ptr), nbytes,
+                                                   1 if on_device else 0), self.h, "pf_decode_row_group_filter")
+        elif windows is None:
             check(lib().pf_decode_row_group(self.h, arr, len(descs), C.c_void_p(buf_ptr), nbytes, 1 if on_device else 0),
                   self.h, "pf_decode_row_group")
         else:
@@ -297,6 +434,25 @@ class GpuDecoder:
             check(lib().pf_decode_row_group_rows(self.h, arr, len(descs), win, C.c_void_p(buf_ptr), nbytes,
                                                  1 if on_device else 0), self.h, "pf_decode_row_group_rows")
         self.n_chunks = len(descs)
+
+    def selection(self):
+        """(rows_in, the selected row numbers as np.int32, ascending, counted from the window's first row) of the last
+        filtered decode, after wait()."""
+        si = self.selection_info()
+        rows = np.zeros(si.rows_selected, np.int32)
+        check(lib().pf_copy_selection(self.h, rows.ctypes.data if rows.size else None, rows.nbytes), self.h, "pf_copy_selection")
+        return si.rows_in, rows
+
+    def selection_info(self):
+        si = SelectionInfo()
+        check(lib().pf_selection_info_get(self.h, C.byref(si)), self.h, "pf_selection_info_get")
+        return si
+
+    def filter_ms(self):
+        """Time of the filter kernels of the last decode (HIP events, ms; 0 without predicates or timing)."""
+        ms = C.c_float()
+        check(lib().pf_debug_filter(self.h, C.byref(ms)), self.h, "pf_debug_filter")
+        return ms.value
 
     def window_ms(self):
         """Time of the window kernels of the last decode (HIP events, ms; 0 without windows or timing)."""
@@ -485,28 +641,48 @@ class GpuDecoder:
         return out
 
 
-def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, rows=None):
+def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, rows=None, where=None):
     """Decode the selected chunks of a file on the GPU: {(rg, col): arrays}. One batch.
     rows=(lo, hi): rows [lo, hi) of ONE row group (row_groups names it; default 0), counted within it: only the
-    pages its OffsetIndex selects are read and uploaded, and the arrays are cut to the rows on the GPU."""
+    pages its OffsetIndex selects are read and uploaded, and the arrays are cut to the rows on the GPU.
+    where=[pfloor.predicate ...]: a conjunction, also over ONE row group (after rows, if given): the page index and the
+    Bloom filters prune first (ParquetFile.prune_row_group), the predicates are evaluated on the GPU and the arrays
+    hold the matching rows only. "_selection" = (rows_in, row numbers within the row group as np.int64), "_range" =
+    the rows that were decoded, None when the row group was skipped (no chunk is returned then). A predicate column
+    outside `columns` is decoded and not returned."""
     with ParquetFile(path) as pf:
         rgs = list(range(pf.num_row_groups)) if row_groups is None else list(row_groups)
         cols = list(range(pf.num_columns)) if columns is None else list(columns)
         dec = decoder or GpuDecoder(device)
         try:
-            if rows is not None:
+            if rows is not None or where is not None:
                 rg = 0 if row_groups is None else rgs[0]
                 if row_groups is not None and len(rgs) != 1:
-                    raise ValueError("rows=(lo, hi) reads one row group")
-                items, total, windows = pf.plan_rows(rg, cols, rows[0], rows[1])
+                    raise ValueError("rows=(lo, hi) and where= read one row group")
+                lo, hi = (0, pf.row_group_rows(rg)) if rows is None else (int(rows[0]), int(rows[1]))
+                batch, preds = list(cols), None
+                if where is not None:
+                    from .predicate import bind, resolve
+                    batch += [c for c in dict.fromkeys(resolve(pf.columns, p.column) for p in where) if c not in cols]
+                    preds = bind(where, pf.columns, {c: i for i, c in enumerate(batch)})
+                    span = pf.prune_row_group(rg, where, lo, hi)
+                    if span is None:
+                        return {"_status": 0, "_error": "", "_selection": (0, np.zeros(0, np.int64)), "_range": None}
+                    lo, hi = span
+                items, total, windows = pf.plan_rows(rg, batch, lo, hi)
                 buf = dec.staging(total)
                 pf.read_rows(items, buf.ptr.value)
-                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=windows)
+                extra = {} if preds is None else {"predicates": preds}
+                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=windows, **extra)
                 rc = dec.wait()
                 out = {}
-                for i, (col, *_r) in enumerate(items):
+                for i, col in enumerate(cols):
                     c = pf.columns[col]
                     out[(rg, col)] = dec.fetch(i, c.physical_type, c.max_def, c.max_rep)
+                if where is not None:
+                    rows_in, sel = dec.selection()
+                    out["_selection"] = (rows_in, sel.astype(np.int64) + lo)
+                    out["_range"] = (lo, hi)
                 out["_status"] = rc
                 out["_error"] = dec.error() if rc else ""
                 return out

@@ -226,9 +226,14 @@ class RowGroupPipeline:
 
     windows: per entry of row_groups None (the whole row group, the path above) or (lo, hi), rows within that row
     group: only the pages its OffsetIndex selects are read and uploaded (ParquetFile.plan_rows) and the columns are cut
-    to the rows on the GPU before they cross the link (GpuDecoder.decode(windows=...))."""
+    to the rows on the GPU before they cross the link (GpuDecoder.decode(windows=...)).
 
-    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None):
+    where: a conjunction of pfloor.predicate predicates. Every row group then goes through plan_rows over its window (or
+    all of it) and GpuDecoder.decode(windows=, predicates=): the predicates are evaluated on the GPU and the columns come
+    back compacted to the matching rows. A predicate column that is not among `columns` is decoded and not returned.
+    `selections[i]` = (rows_in, rows_selected) of row_groups[i] once taken; `bytes_read` counts the chunk bytes read."""
+
+    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None, where=None):
         if not devices:
             raise ValueError("devices must not be empty")
         self.reader = reader
@@ -237,6 +242,16 @@ class RowGroupPipeline:
         self.windows = list(windows) if windows is not None else [None] * len(self.row_groups)
         if len(self.windows) != len(self.row_groups):
             raise ValueError("one window (or None) per row group")
+        self.where = list(where) if where else None
+        self.selections = {}
+        self.bytes_read = 0
+        self._batch = [c.index for c in columns]
+        self._preds = None
+        if self.where:
+            from .predicate import bind, resolve
+            extra = dict.fromkeys(resolve(reader.columns, p.column) for p in self.where)
+            self._batch += [c for c in extra if c not in self._batch]
+            self._preds = bind(self.where, reader.columns, {c: i for i, c in enumerate(self._batch)})
         self.depth = max(1, int(depth))
         self.decs = []   # [device slot][k]
         self.inflight = collections.OrderedDict()   # position in row_groups -> decoder, or the enqueue error
@@ -261,12 +276,13 @@ class RowGroupPipeline:
         dec = self._decoder(i)
         try:
             idx = [c.index for c in self.columns]
-            if self.windows[i] is not None:
-                lo, hi = self.windows[i]
-                items, total, wins = self.reader.plan_rows(rg, idx, lo, hi)
+            if self.windows[i] is not None or self._preds is not None:
+                lo, hi = self.windows[i] if self.windows[i] is not None else (0, self.reader.row_group_rows(rg))
+                items, total, wins = self.reader.plan_rows(rg, self._batch, lo, hi)
                 buf = dec.staging(total)
-                self.reader.read_rows(items, buf.ptr.value)
-                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=wins)
+                self.bytes_read += self.reader.read_rows(items, buf.ptr.value)
+                extra = {} if self._preds is None else {"predicates": self._preds}
+                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=wins, **extra)
                 self.inflight[i] = dec
                 return
             items, total = self.reader.plan([rg], idx)
@@ -293,6 +309,9 @@ class RowGroupPipeline:
         rc = dec.wait()
         if rc != 0:
             raise RuntimeError(dec.error())
+        if self._preds is not None:
+            si = dec.selection_info()
+            self.selections[i] = (si.rows_in, si.rows_selected)
         return [dec.fetch(k, c.physical_type, c.max_def, c.max_rep) for k, c in enumerate(self.columns)]
 
     def close(self):
@@ -311,16 +330,21 @@ class ParquetReader:
 
     # --- static factories (ParquetReader.java:47-84) ---
     @staticmethod
-    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None):
-        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices, rows))
+    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None):
+        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices, rows, where))
 
     @staticmethod
-    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None):
+    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None):
         """devices: GPUs to deal the row groups over (default [device]); rows stay in file order.
         rows=(lo, hi): only rows lo .. hi-1 of the file (0 <= lo <= hi <= num_rows): row groups wholly outside are
-        neither read nor decoded, the two edge row groups are read by page and cut on the GPU, inner ones as ever."""
+        neither read nor decoded, the two edge row groups are read by page and cut on the GPU, inner ones as ever.
+        where=[pfloor.predicate ...]: only the rows that match the conjunction. After `rows`, the page index and the
+        Bloom filters prune every row group (ParquetFile.prune_row_group: a skipped one is neither read nor decoded);
+        the rest are read by page over what remains, filtered on the GPU and compacted there, so only matching rows
+        cross the link. A predicate column outside `columns` is decoded and never passed to the Hydrator. A projected
+        or predicate column with repetition is an IllegalArgumentException. `filter_stats` counts what happened."""
         column_set = frozenset() if columns is None else frozenset(columns)
-        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices, rows)
+        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices, rows, where)
 
     @staticmethod
     def stream(reader):
@@ -359,7 +383,7 @@ class ParquetReader:
         return f
 
     # --- instance (ParquetReader.java:119-131) ---
-    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None, rows=None):
+    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None, rows=None, where=None):
         try:
             self.reader = ParquetFile(path)
         except Exception as e:
@@ -389,7 +413,40 @@ class ParquetReader:
                 if a < b:
                     self._visits.append((rg, None if (a, b) == (0, n) else (a, b)))
                 start += n
+        self._where = list(where) if where else None
+        self.filter_stats = {"row_groups_skipped_index": 0, "row_groups_skipped_bloom": 0, "bytes_read": 0, "rows_decoded": 0,
+                             "rows_selected": 0}
+        if self._where:
+            try:
+                self._prune_visits()
+            except Exception:
+                self.reader.close()
+                raise
         self._pos = -1
+
+    def _prune_visits(self):
+        """where=: refuse repetition, then narrow or drop every visit by the page index and the Bloom filters."""
+        from .predicate import resolve
+        try:
+            pred_cols = [self.reader.columns[resolve(self.reader.columns, p.column)] for p in self._where]
+        except ValueError as e:
+            raise IllegalArgumentException(str(e)) from e
+        for c in list(self.columns) + pred_cols:
+            if c.max_rep > 0:
+                raise IllegalArgumentException(f"where=: column {'.'.join(c.path)} has repetition")
+        kept = []
+        for rg, win in self._visits:
+            n = self.reader.row_group_rows(rg)
+            lo, hi = win if win is not None else (0, n)
+            try:
+                span, why = self.reader._prune(rg, self._where, lo, hi)
+            except ValueError as e:
+                raise IllegalArgumentException(str(e)) from e
+            if span is None:
+                self.filter_stats["row_groups_skipped_" + why] += 1
+            else:
+                kept.append((rg, span))
+        self._visits = kept
 
     def _read_next_row_group(self):
         self._pos += 1
@@ -403,11 +460,19 @@ class ParquetReader:
             raise RuntimeError("Illegal row group of 0 rows")
         if self._pipe is None:
             self._pipe = RowGroupPipeline(self.reader, self.columns, [v[0] for v in self._visits], self._devices,
-                                          windows=[v[1] for v in self._visits])
+                                          windows=[v[1] for v in self._visits], where=self._where)
         arrays = self._pipe.take(self._pos)
         self.cursors = [_ColumnCursor(c, a) for c, a in zip(self.columns, arrays)]
         self.current_row_group_size = self.reader.row_group_rows(rg) if win is None else win[1] - win[0]
         self.current_row_index = 0
+        if self._where:
+            rows_in, selected = self._pipe.selections.pop(self._pos)
+            self.filter_stats["rows_decoded"] += rows_in
+            self.filter_stats["rows_selected"] += selected
+            self.filter_stats["bytes_read"] = self._pipe.bytes_read + getattr(self.reader, "bloom_bytes_read", 0)
+            self.current_row_group_size = selected
+            if selected == 0:   # nothing of this row group matches: on to the next
+                return self._read_next_row_group()
         return True
 
     def tryAdvance(self, action):
