@@ -1,6 +1,6 @@
 // pf_crc.h — CRC-32 arithmetic (reflected polynomial 0xEDB88320, as zlib / java.util.zip.CRC32) shared by
 // the read side (pf_scan.hip: k_page_crc verifies PageHeader.crc), the write side (pf_enc_crc.hip: k_enc_crc
-// computes the pieces of a page) and the host fold of those pieces (pf_runtime.hip). Internal.
+// computes the pieces of a page) and the host fold of those pieces (pf_enc_plan.cpp). Internal.
 //
 // A raw CRC (zero init, no final xor) is linear in the data: raw(A ‖ B) = raw(A) * x^(8 |B|) + raw(B) mod P,
 // so the pieces of a page are reduced independently and folded in order.

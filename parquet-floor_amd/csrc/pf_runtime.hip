@@ -6,7 +6,8 @@
 // SnappyJob tables, launch lists and arena sizes; this file grows the arenas to those sizes, has
 // the planner bind its offsets to them, uploads the tables in one copy, and enqueues
 //   k_snappy / k_zstd -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
-// on the context stream. Nothing synchronises until pf_wait.
+// on the context stream. Nothing synchronises until pf_wait. The context itself is pf_ctx.h; the write path
+// is a unit of its own, pf_enc_runtime.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,14 +20,11 @@
 #include <string>
 #include <vector>
 
-#include "pf_crc.h"
-#include "pf_encode.h"
+#include "pf_ctx.h"
 #include "pf_host.h"
 #include "pf_launch.h"
 #include "pf_plan.h"
 #include "pf_snappy_par.h"
-#include "pf_xxh64.h"
-#include "pf_zstd_enc_core.h"
 #include "pfloor.h"
 
 using namespace pf;
@@ -36,40 +34,6 @@ static_assert(sizeof(Int2) == sizeof(int2) && alignof(Int2) <= alignof(int2), "t
 namespace {
 
 thread_local std::string g_err;
-
-int fail(pf_ctx* ctx, int code, const std::string& msg);
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = std::max<size_t>(n + n / 4, 1 << 20);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-struct HostBuf {
-    void* p = nullptr;
-    void* d = nullptr;   // the device's address of the pinned pages (kernels read / write them over PCIe)
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; d = nullptr; cap = 0; }
-        size_t want = std::max<size_t>(n + n / 4, 1 << 16);
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) {
-            cap = want;
-            if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) d = nullptr;
-        }
-        return e;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; d = nullptr; cap = 0; }
-};
 
 // Copies between pinned host pages and device memory by a kernel on the decode stream: two ranges
 // of 8-byte words, grid-stride. The batch's metadata upload and its results download were SDMA /
@@ -133,112 +97,17 @@ __global__ __launch_bounds__(256) void k_download(DlRange r0, DlRange r1, DlRang
     }
 }
 
-constexpr int N_EVENTS = 11;  // h2d, snappy parse, snappy exec, dict, delta, levels, count, scan, flat, decode
-
 }  // namespace
 
-// The HIP streams of a context. Shared by contexts made with pf_ctx_create_shared (the stream
-// lives until the last of them is destroyed).
-struct Streams {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // pf_copy_batch_async's downloads (made on first use): the next batch's H2D and kernels on `stream`
-    // (a twin context's, with its own arenas) run while this batch's columns go to the host
-    hipStream_t copy_stream = nullptr;
-    std::mutex mu;
-    ~Streams() {
-        (void)hipSetDevice(device);
-        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-    }
-};
-
-struct pf_ctx {
-    int device = 0;
-    pf::PfOpts opts;                       // defaults; the diagnostics build reads PF_* at creation
-    std::shared_ptr<Streams> streams;
-    hipStream_t stream = nullptr;          // = streams->stream
-    bool zc = true;                        // metadata / results copied by k_copy_words (PF_ZC=0: SDMA copies)
-    hipEvent_t ev[N_EVENTS] = {};
-    // recorded after the last operation of this context's decode: pf_wait waits for it, not for the
-    // stream, so a context sharing the stream can have the next batch enqueued behind this one
-    hipEvent_t ev_done = nullptr;
-    // recorded after the last enqueued D2H copy of this context's outputs: pf_copy_column / pf_sync
-    // wait for it, not for the stream, so a peer's decode queued behind the copies keeps running
-    hipEvent_t ev_copy = nullptr;          // after this context's last async copy (on whichever stream)
-    hipEvent_t ev_dl = nullptr;            // the decode a download on the copy stream follows
-    hipEvent_t ev_bloom[2] = {};           // pf_encode_chunk: around the Bloom filter's fill (pf_encoded_chunk.bloom_ms)
-    bool timing = true;                    // per-stage events (pf_last_timing); pf_ctx_set_timing
-    std::string err;
-    DevBuf d_in, d_scratch, d_out, d_bits, d_chars, d_meta, d_tokmap;
-    DevBuf d_scan_in, d_scan;              // pf_scan_pages: host chunk bytes, tables
-    DevBuf d_enc, d_enc_sec, d_enc_out;    // pf_encode_chunk / pf_snappy_compress: work arena, values sections, slots
-    std::vector<uint8_t> h_enc;            // the last encoded chunk (headers + bodies)
-    std::vector<uint8_t> h_enc_stat;       // its chunk statistics (min ‖ max)
-    HostBuf h_enc_st;                      // pf_encode_chunk: statistics results D2H
-    HostBuf h_enc_bloom;                   // pf_encode_chunk: the Bloom filter's bitset D2H (pf_encoded_chunk.bloom)
-    HostBuf h_meta, h_res;
-    HostBuf h_enc_slots;                   // pf_encode_chunk / pf_snappy_compress: compressed slots D2H
-    // last batch
-    int n_chunks = 0;
-    bool pending = false;
-    bool copies_pending = false;           // pf_copy_columns_async enqueued, not yet pf_sync'ed
-    bool tables_from_decode = false;       // d_meta layout (off_fallback) belongs to a pf_decode_row_group
-    bool timing_valid = false;
-    pf::BatchPlan plan;                    // the last pf_decode_row_group's tables, lists and layout
-    // diagnostics: tables of the last pf_snappy_decompress (pf_debug_snappy_tables)
-    const uint32_t* d_last_splits = nullptr;
-    const SnapWin* d_last_win = nullptr;
-    const uint32_t* d_last_lane_out = nullptr;
-    std::vector<pf_column_info> info;
-    bool meta_by_kernel = false;   // this batch's metadata went up by k_upload (which also zeroes bits / npub)
-    uint64_t chars_need = 0;
-    int reruns = 0;
-    HostBuf h_enc_px;                      // pf_encode_chunk: the page index block D2H (pf_encoded_chunk.index_*)
-    std::vector<int64_t> h_enc_pgoff, h_enc_pgrow;   // pf_encoded_chunk.page_offset / page_first_row
-    std::vector<int32_t> h_enc_pgsize;               // pf_encoded_chunk.page_size
-    // row windows (pf_decode_row_group_rows): the chunks whose window is not {0, -1}, their tables, and the twin output
-    // arenas k_win_copy writes (allocated only for a batch that has such a window)
-    std::vector<DevWin> wins;
-    DevBuf d_win, d_wout, d_wbits, d_wchars;
-    HostBuf h_win;                         // DevWin[n] up, DevWinRes[n] down
-    int win_grid = 1;
-    hipEvent_t ev_win[2] = {};
-    // row filter (pf_decode_row_group_filter): the packed predicates (none: no filter stage), the stage's device buffer
-    // and its pinned mirror: [DevSelHead | DevSelChunk[n]] comes down, [DevPred[] | blob | win_of[n]] goes up
-    pf::FilterPlan filt;
-    DevBuf d_sel;
-    HostBuf h_sel;
-    pf::SelBufs sel{};
-    size_t sel_up_off = 0;                 // where the uploaded tables begin: the bytes before them come down
-    int sel_grid = 1;
-    hipEvent_t ev_sel[2] = {};
-    pf_selection_info sel_info{};
-    bool filtered() const { return !filt.preds.empty(); }
-    bool twins() const { return !wins.empty() || filtered(); }   // the batch's results are not (all) in the decode arenas
-};
-
-namespace {
-
+namespace pf {
 int fail(pf_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg;
     g_err = msg;
     return code;
 }
+}  // namespace pf
 
-#define HIPCHK(ctx, expr)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ctx, PF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// stage-timing event: only when the context has timing on (each record is a marker on the stream,
-// ~7 us between kernels on MI355X, so the product path leaves them off)
-#define EVREC(ctx, ev, st)                                 \
-    do {                                                   \
-        if ((ctx)->timing) HIPCHK(ctx, hipEventRecord(ev, st)); \
-    } while (0)
+namespace {
 
 // k_count / k_decode blocks when no page is known to need them: both stride over their whole list,
 // and nearly every page was taken by another kernel (k_count_flat, the flat kernels)
@@ -443,848 +312,7 @@ int input_to_device(pf_ctx* ctx, const uint8_t* bytes, size_t n_bytes) {
 }  // namespace
 
 
-// ---------------------------------------------------------------- write path (pf_encode.hip)
-namespace {
-size_t uvarint_len(uint64_t v) { size_t k = 1; while (v >= 0x80) { v >>= 7; k++; } return k; }
-void put_uvarint(std::vector<uint8_t>& o, uint64_t v) {
-    while (v >= 0x80) { o.push_back(uint8_t(v | 0x80)); v >>= 7; }
-    o.push_back(uint8_t(v));
-}
-
-// Bytes the host puts in front of a section's jobs: Snappy's length varint, or ZSTD's frame header (and for
-// a section of 0 bytes, which has no job, the one empty last raw block).
-size_t stream_head(int codec, uint64_t n, uint8_t* o /* 12 bytes */) {
-    if (codec == PF_CODEC_ZSTD) {
-        size_t k = zstd::frame_header_put(n, o);
-        if (n == 0) { std::memcpy(o + k, zstd::ZE_EMPTY_BLOCK, 3); k += 3; }
-        return k;
-    }
-    size_t k = 0;
-    while (n >= 0x80) { o[k++] = uint8_t(n | 0x80); n >>= 7; }
-    o[k++] = uint8_t(n);
-    return k;
-}
-
-// Compress `sections` (device, each [off, off + len) of `base`) with `codec` (PF_CODEC_SNAPPY | PF_CODEC_ZSTD)
-// into the slots of independent jobs of SC_BLOCK / ZC_BLOCK bytes; returns per section the host stream (Snappy:
-// varint length + block outputs; ZSTD: frame header + the jobs' blocks) in `streams`.
-// With `crc_out` (PF_ENCODE_PAGE_CRC): k_enc_crc right behind the compressor over every job's slot, in job
-// order, then over `extra`; the results come back in the copy that brings the jobs' lengths.
-int compress_sections(pf_ctx* ctx, const uint8_t* base, const std::vector<std::pair<uint64_t, uint64_t>>& sections,
-                      std::vector<std::vector<uint8_t>>& streams, int codec, float* kernel_ms = nullptr,
-                      const std::vector<CrcPiece>* extra = nullptr, std::vector<CrcOut>* crc_out = nullptr, float* crc_ms = nullptr) {
-    hipStream_t st = ctx->stream;
-    const bool zs = codec == PF_CODEC_ZSTD;
-    const uint32_t JOB = zs ? ZC_BLOCK : SC_BLOCK, SLOT = zs ? ZC_SLOT : SC_SLOT;
-    std::vector<CompJob> jobs;
-    std::vector<std::pair<size_t, size_t>> range(sections.size());   // jobs of each section
-    for (size_t i = 0; i < sections.size(); i++) {
-        range[i].first = jobs.size();
-        for (uint64_t o = 0; o < sections[i].second; o += JOB) {
-            CompJob j{};
-            j.src = base + sections[i].first + o;
-            j.len = uint32_t(std::min<uint64_t>(JOB, sections[i].second - o));
-            j.last = zs && o + j.len == sections[i].second;
-            jobs.push_back(j);
-        }
-        range[i].second = jobs.size();
-    }
-    const size_t nj = jobs.size();
-    size_t m = 0;
-    auto take = [](size_t& cur, size_t sz) { size_t o = align_up(cur, 256); cur = o + sz; return o; };
-    const size_t o_jobs = take(m, sizeof(CompJob) * std::max<size_t>(nj, 1));
-    // the jobs' lengths and, behind them, the pieces' CRCs: one D2H
-    const size_t np = crc_out ? nj + (extra ? extra->size() : 0) : 0;
-    const size_t o_crc_in_len = align_up(4 * nj, 16);
-    const size_t len_bytes = np ? o_crc_in_len + sizeof(CrcOut) * np : 4 * std::max<size_t>(nj, 1);
-    const size_t o_len = take(m, len_bytes);
-    const size_t o_pieces = take(m, sizeof(CrcPiece) * std::max<size_t>(np, 1));
-    const size_t o_slots = take(m, size_t(SLOT) * std::max<size_t>(nj, 1));
-    HIPCHK(ctx, ctx->d_enc_out.ensure(m));
-    uint8_t* d = static_cast<uint8_t*>(ctx->d_enc_out.p);
-    for (size_t k = 0; k < nj; k++) jobs[k].dst = d + o_slots + k * SLOT;
-    // compressed lengths + slots come back into the context's pinned staging (no zero-fill, DMA speed)
-    HIPCHK(ctx, ctx->h_enc_slots.ensure(align_up(len_bytes, 256) + nj * size_t(SLOT)));
-    uint32_t* lens = static_cast<uint32_t*>(ctx->h_enc_slots.p);
-    uint8_t* slots = static_cast<uint8_t*>(ctx->h_enc_slots.p) + align_up(len_bytes, 256);
-    std::vector<CrcPiece> pieces(np);
-    if (nj) {
-        HIPCHK(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(CompJob) * nj, hipMemcpyHostToDevice, st));
-        EVREC(ctx, ctx->ev[0], st);
-        (zs ? launch_zstd_compress : launch_snappy_compress)(reinterpret_cast<const CompJob*>(d + o_jobs), int(nj), reinterpret_cast<uint32_t*>(d + o_len), st);
-        HIPCHK(ctx, hipGetLastError());
-        EVREC(ctx, ctx->ev[1], st);
-    }
-    if (np) {
-        const uint32_t* d_len = reinterpret_cast<const uint32_t*>(d + o_len);
-        for (size_t k = 0; k < nj; k++) pieces[k] = CrcPiece{jobs[k].dst, d_len + k, 0u, SLOT};
-        for (size_t k = nj; k < np; k++) pieces[k] = (*extra)[k - nj];
-        HIPCHK(ctx, hipMemcpyAsync(d + o_pieces, pieces.data(), sizeof(CrcPiece) * np, hipMemcpyHostToDevice, st));
-        EVREC(ctx, ctx->ev[8], st);
-        launch_enc_crc(reinterpret_cast<const CrcPiece*>(d + o_pieces), int(np), reinterpret_cast<CrcOut*>(d + o_len + o_crc_in_len), st);
-        HIPCHK(ctx, hipGetLastError());
-        EVREC(ctx, ctx->ev[9], st);
-    }
-    if (nj || np) HIPCHK(ctx, hipMemcpyAsync(lens, d + o_len, np ? len_bytes : 4 * nj, hipMemcpyDeviceToHost, st));
-    if (nj) HIPCHK(ctx, hipMemcpyAsync(slots, d + o_slots, nj * size_t(SLOT), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (crc_out) {
-        const CrcOut* h = reinterpret_cast<const CrcOut*>(reinterpret_cast<const uint8_t*>(lens) + o_crc_in_len);
-        crc_out->assign(h, h + np);
-    }
-    if (crc_ms) {
-        *crc_ms = 0.f;
-        if (ctx->timing && np) HIPCHK(ctx, hipEventElapsedTime(crc_ms, ctx->ev[8], ctx->ev[9]));
-    }
-    if (kernel_ms) {
-        *kernel_ms = 0.f;
-        if (ctx->timing && nj) HIPCHK(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]));
-    }
-    streams.assign(sections.size(), {});
-    for (size_t i = 0; i < sections.size(); i++) {
-        std::vector<uint8_t>& o = streams[i];
-        uint8_t head[12];
-        o.assign(head, head + stream_head(codec, sections[i].second, head));
-        for (size_t k = range[i].first; k < range[i].second; k++) {
-            if (lens[k] > (zs ? 3 + jobs[k].len : SLOT)) return fail(ctx, PF_ERR_HIP, zs ? "zstd compress: block overflow" : "snappy compress: block overflow");
-            const uint8_t* b = slots + k * size_t(SLOT);
-            o.insert(o.end(), b, b + lens[k]);
-        }
-    }
-    return PF_OK;
-}
-}  // namespace
-
-extern "C" int pf_snappy_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len) {
-    if (!ctx || (!src && n) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
-    if (n > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "snappy: buffer too large");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
-    ctx->copies_pending = false;
-    HIPCHK(ctx, ctx->d_enc.ensure(std::max<size_t>(n, 1)));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_enc.p, src, n, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<std::vector<uint8_t>> streams;
-    const int rc = compress_sections(ctx, static_cast<const uint8_t*>(ctx->d_enc.p), {{0, n}}, streams, PF_CODEC_SNAPPY);
-    if (rc) return rc;
-    *out_len = streams[0].size();
-    if (streams[0].size() > cap) return fail(ctx, PF_ERR_CAPACITY, "snappy: destination too small");
-    std::memcpy(dst, streams[0].data(), streams[0].size());
-    return PF_OK;
-}
-
-extern "C" int pf_zstd_compress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len) {
-    if (!ctx || (!src && n) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
-    if (n > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "zstd: buffer too large");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
-    ctx->copies_pending = false;
-    HIPCHK(ctx, ctx->d_enc.ensure(std::max<size_t>(n, 1)));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_enc.p, src, n, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<std::vector<uint8_t>> streams;
-    const int rc = compress_sections(ctx, static_cast<const uint8_t*>(ctx->d_enc.p), {{0, n}}, streams, PF_CODEC_ZSTD);
-    if (rc) return rc;
-    *out_len = streams[0].size();
-    if (streams[0].size() > cap) return fail(ctx, PF_ERR_CAPACITY, "zstd: destination too small");
-    std::memcpy(dst, streams[0].data(), streams[0].size());
-    return PF_OK;
-}
-
-extern "C" int pf_encode_chunk(pf_ctx* ctx, const pf_encode_column* col, int on_device, pf_encoded_chunk* out) {
-    if (!ctx || !col || !out) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
-    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
-    const int pt = col->physical_type;
-    if (pt != PF_BOOLEAN && pt != PF_INT32 && pt != PF_INT64 && pt != PF_FLOAT && pt != PF_DOUBLE && pt != PF_BYTE_ARRAY)
-        return fail(ctx, PF_ERR_UNSUPPORTED_TYPE, "encode: unsupported physical type");
-    const int64_t n = col->num_rows;
-    if (n < 0 || n > 0x7ffffff0 || (col->max_def != 0 && col->max_def != 1)) return fail(ctx, PF_ERR_INVALID_ARG, "encode: bad shape");
-    if (col->codec != PF_CODEC_SNAPPY && col->codec != PF_CODEC_ZSTD && col->codec != PF_CODEC_UNCOMPRESSED)
-        return fail(ctx, PF_ERR_UNSUPPORTED_CODEC, "encode: codec must be SNAPPY, ZSTD or UNCOMPRESSED");
-    const bool compressed = col->codec != PF_CODEC_UNCOMPRESSED;
-    if (col->bloom_bytes != 0 && (col->bloom_bytes < 0 || !bloom_size_ok(uint64_t(col->bloom_bytes))))
-        return fail(ctx, PF_ERR_INVALID_ARG, "encode: bloom_bytes must be a power of two in [32, 128 MiB]");
-    const size_t bloom = pt == PF_BOOLEAN ? 0 : size_t(col->bloom_bytes);   // BOOLEAN: no filter (parquet-mr builds none)
-    const bool str = pt == PF_BYTE_ARRAY;
-    const bool want_index = (col->dictionary & PF_ENCODE_PAGE_INDEX) != 0;
-    if (want_index && str && col->index_truncate != 0 && col->index_truncate != -1 &&
-        (col->index_truncate < 1 || col->index_truncate > 2047))
-        return fail(ctx, PF_ERR_INVALID_ARG, "encode: index_truncate must be 0, -1 or in [1, 2047]");
-    const uint32_t px_trunc = col->index_truncate == -1 ? PX_NO_TRUNC : col->index_truncate == 0 ? 64u : uint32_t(col->index_truncate);
-    if (n > 0 && (str ? (!col->offsets || (!col->chars && col->chars_len > 0) || col->chars_len < 0 || col->chars_len > 0x7fffffff)
-                      : !col->values))
-        return fail(ctx, PF_ERR_INVALID_ARG, "encode: missing input arrays");
-    const int w = pt == PF_BOOLEAN ? 1 : type_width(pt, 0);
-    int64_t page_rows = col->page_rows > 0 ? col->page_rows : 20000;
-    page_rows = (page_rows + 7) / 8 * 8;   // definition levels of a page start on a validity byte
-    // dictionary page limit (parquet.dictionary.page.size, 1 MiB); capped so a dictionary that passes it
-    // always fits the 32-bit offsets of the dictionary kernels
-    const int64_t dict_limit = std::min<int64_t>(col->dict_page_limit > 0 ? col->dict_page_limit : (1 << 20), 0x7fffffff);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
-    ctx->copies_pending = false;
-
-    // host copies of validity / offsets (page plan, definition levels)
-    const size_t vbytes = size_t((n + 7) / 8);
-    std::vector<uint8_t> hval;
-    std::vector<int32_t> hoff;
-    const bool has_val = col->max_def == 1 && col->validity;
-    if (has_val) {
-        hval.resize(vbytes);
-        if (on_device) HIPCHK(ctx, hipMemcpy(hval.data(), col->validity, vbytes, hipMemcpyDeviceToHost));
-        else std::memcpy(hval.data(), col->validity, vbytes);
-    }
-    if (str && n > 0) {
-        hoff.resize(size_t(n) + 1);
-        if (on_device) HIPCHK(ctx, hipMemcpy(hoff.data(), col->offsets, 4 * (size_t(n) + 1), hipMemcpyDeviceToHost));
-        else std::memcpy(hoff.data(), col->offsets, 4 * (size_t(n) + 1));
-        for (int64_t r = 0; r < n; r++)
-            if (hoff[r + 1] < hoff[r] || hoff[r] < 0 || hoff[r + 1] > col->chars_len)
-                return fail(ctx, PF_ERR_INVALID_ARG, "encode: offsets out of order or outside chars");
-    }
-    auto present = [&](int64_t r) { return !has_val || ((hval[size_t(r >> 3)] >> (r & 7)) & 1); };
-    // page plan: rows, present values, PLAIN byte sizes
-    struct PagePlanE { int64_t r0, r1; uint32_t d0, cnt; uint64_t plain; };
-    std::vector<PagePlanE> pp;
-    uint32_t m = 0;
-    for (int64_t r0 = 0; r0 < n || (n == 0 && pp.empty()); r0 += page_rows) {
-        PagePlanE p{r0, std::min(n, r0 + page_rows), m, 0, 0};
-        for (int64_t r = p.r0; r < p.r1; r++)
-            if (present(r)) {
-                p.cnt++;
-                if (str) p.plain += 4 + uint64_t(hoff[r + 1] - hoff[r]);
-            }
-        if (!str) p.plain = pt == PF_BOOLEAN ? (p.cnt + 7) / 8 : uint64_t(p.cnt) * w;
-        m += p.cnt;
-        pp.push_back(p);
-        if (n == 0) break;
-    }
-    // DELTA_* fallback (PF_ENCODE_DELTA_FALLBACK): one stream per integer page, two (prefix lengths,
-    // suffix lengths) per string page; an item of the size table is a stream header or a 128-delta block
-    const bool delta_bit = (col->dictionary & PF_ENCODE_DELTA_FALLBACK) && (pt == PF_INT32 || pt == PF_INT64 || str);
-    std::vector<DeltaStream> dstreams;
-    std::vector<DeltaPage> dpages;
-    uint32_t n_items = 0;
-    if (delta_bit) {
-        for (size_t i = 0; i < pp.size(); i++) {
-            const PagePlanE& p = pp[i];
-            const uint32_t ns = str ? 2u : 1u, blocks = p.cnt > 1 ? (p.cnt - 1 + 127) / 128 : 0u;
-            // worst case of the values section (every block: zigzag(min) + widths + full-width values)
-            const uint64_t worst = ns * (25ull + blocks * 14ull + uint64_t(p.cnt) * (str ? 4 : w)) + (str ? p.plain : 0);
-            if (worst > 0x7fffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
-            dpages.push_back(DeltaPage{0, p.d0, p.cnt, uint32_t(dstreams.size()), ns});
-            for (uint32_t k = 0; k < ns; k++) {
-                dstreams.push_back(DeltaStream{nullptr, uint32_t(str ? 4 : w), p.cnt, uint32_t(i), n_items});
-                n_items += 1 + blocks;
-            }
-        }
-        dstreams.push_back(DeltaStream{nullptr, 0, 0, 0, n_items});
-    }
-    // parquet-mr's hybrid runs (PF_ENCODE_HYBRID_RUNS): a page has a stream of levels (OPTIONAL) and one of
-    // ids or BOOLEAN values
-    const bool hyb = (col->dictionary & PF_ENCODE_HYBRID_RUNS) != 0;
-    const size_t n_hs_max = hyb ? 2 * pp.size() : 0;
-    // statistics (PF_ENCODE_STATISTICS): a workgroup per (page, tile of ST_TILE present values)
-    const bool want_stats = (col->dictionary & PF_ENCODE_STATISTICS) != 0;
-    const bool want_crc = (col->dictionary & PF_ENCODE_PAGE_CRC) != 0;
-    const bool run_stats = want_stats || want_index;   // the page index is built from the statistics kernels' page results
-    std::vector<StatTile> stiles;
-    std::vector<uint32_t> sptile;
-    if (run_stats) {
-        for (size_t i = 0; i < pp.size(); i++) {
-            sptile.push_back(uint32_t(stiles.size()));
-            for (uint32_t o = 0; o < pp[i].cnt; o += ST_TILE)
-                stiles.push_back(StatTile{uint32_t(i), pp[i].d0 + o, std::min(ST_TILE, pp[i].cnt - o), 0u});
-        }
-        sptile.push_back(uint32_t(stiles.size()));
-    }
-    const size_t n_se = run_stats ? pp.size() + 1 : 0;   // statistics entries: the pages, then the chunk
-    // page index (PF_ENCODE_PAGE_INDEX): the pages' rows and present values go up, one block comes back:
-    // head | null_counts | offsets | null_pages | values (the worst case: every entry as long as it can get)
-    const size_t n_px = want_index ? pp.size() : 0;
-    const uint64_t px_entry = !str ? uint64_t(w) : px_trunc == PX_NO_TRUNC ? uint64_t(ST_LIMIT) / 2 : uint64_t(px_trunc);
-    const uint64_t px_cap = 2 * px_entry * n_px;
-    if (px_cap > 0x40000000ull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: page index values over 1 GiB (fewer pages or a shorter index_truncate)");
-    const size_t px_nc = sizeof(PgIndexHead), px_off = px_nc + 8 * n_px, px_np = px_off + 4 * (2 * n_px + 1), px_val = px_np + n_px;
-    const size_t px_bytes = want_index ? px_val + size_t(px_cap) : 0;
-
-    // ---- device arena ----
-    size_t a_sz = 0;
-    auto take = [](size_t& cur, size_t sz) { size_t o = align_up(cur, 256); cur = o + std::max<size_t>(sz, 1); return o; };
-    const size_t N1 = size_t(n) + 1;
-    const size_t o_in = take(a_sz, str ? 0 : size_t(n) * w), o_vl = take(a_sz, vbytes);
-    const size_t o_of = take(a_sz, str ? 4 * N1 : 0), o_ch = take(a_sz, str ? size_t(col->chars_len) : 0);
-    const size_t o_flag = take(a_sz, 4 * N1), o_pos = take(a_sz, 4 * N1), o_dense = take(a_sz, size_t(n) * w);
-    const size_t o_dsrc = take(a_sz, str ? 4 * N1 : 0), o_dlen = take(a_sz, str ? 4 * N1 : 0);
-    const size_t o_vsz = take(a_sz, str ? 4 * N1 : 0), o_vpre = take(a_sz, str ? 4 * N1 : 0);
-    const size_t o_key = take(a_sz, 8 * N1), o_skey = take(a_sz, 8 * N1), o_didx = take(a_sz, 4 * N1), o_sidx = take(a_sz, 4 * N1);
-    const size_t o_hp = take(a_sz, 4 * N1), o_head = take(a_sz, 4 * N1), o_mark = take(a_sz, 4 * N1), o_did = take(a_sz, 4 * N1);
-    const size_t o_dsz = take(a_sz, 4 * N1), o_doff = take(a_sz, 4 * N1), o_ids = take(a_sz, 4 * N1), o_col = take(a_sz, 256);
-    // DELTA_* tables (only with the bit set): string prefix / suffix lengths and positions, streams, pages,
-    // item bytes and offsets, block minima and widths, page totals
-    const size_t NI1 = delta_bit ? size_t(n_items) + 1 : 0;
-    const size_t o_pfx = take(a_sz, delta_bit && str ? 4 * N1 : 0), o_sfx = take(a_sz, delta_bit && str ? 4 * N1 : 0);
-    const size_t o_spre = take(a_sz, delta_bit && str ? 4 * N1 : 0);
-    const size_t o_dstr = take(a_sz, sizeof(DeltaStream) * dstreams.size()), o_dpg = take(a_sz, sizeof(DeltaPage) * dpages.size());
-    const size_t o_dby = take(a_sz, 4 * NI1), o_dof = take(a_sz, 4 * NI1), o_dmin = take(a_sz, 8 * NI1), o_dwd = take(a_sz, 4 * NI1);
-    const size_t o_dtot = take(a_sz, 4 * dpages.size());
-    const size_t o_hstr = take(a_sz, sizeof(HybridStream) * n_hs_max), o_hby = take(a_sz, 4 * n_hs_max);
-    const size_t o_stt = take(a_sz, sizeof(StatTile) * stiles.size()), o_stp = take(a_sz, 4 * sptile.size());
-    const size_t o_spart = take(a_sz, sizeof(StatPart) * stiles.size()), o_swin = take(a_sz, str ? 8 * stiles.size() : 0);
-    const size_t o_sout = take(a_sz, sizeof(StatPart) * n_se), o_sbytes = take(a_sz, str ? size_t(ST_LIMIT) * n_se : 0);
-    const size_t o_xin = take(a_sz, 8 * n_px), o_xnn = take(a_sz, 4 * n_px), o_xout = take(a_sz, px_bytes);
-    size_t temp_bytes = 0;
-    HIPCHK(ctx, enc_scan_temp(std::max(N1, NI1), temp_bytes));   // the scans over rows, dense values and delta items
-    const size_t o_temp = take(a_sz, temp_bytes);
-    const size_t o_bloom = bloom ? take(a_sz, bloom) : 0;
-    HIPCHK(ctx, ctx->d_enc.ensure(a_sz));
-    uint8_t* A = static_cast<uint8_t*>(ctx->d_enc.p);
-    EncArgs ea{};
-    ea.ptype = pt; ea.width = w; ea.n = n;
-    if (on_device) {
-        ea.values = static_cast<const uint8_t*>(col->values);
-        ea.validity = has_val ? col->validity : nullptr;
-        ea.offsets = col->offsets;
-        ea.chars = col->chars;
-    } else {
-        if (!str && n) HIPCHK(ctx, hipMemcpyAsync(A + o_in, col->values, size_t(n) * w, hipMemcpyHostToDevice, st));
-        if (has_val && vbytes) HIPCHK(ctx, hipMemcpyAsync(A + o_vl, hval.data(), vbytes, hipMemcpyHostToDevice, st));
-        if (str && n) {
-            HIPCHK(ctx, hipMemcpyAsync(A + o_of, hoff.data(), 4 * N1, hipMemcpyHostToDevice, st));
-            if (col->chars_len) HIPCHK(ctx, hipMemcpyAsync(A + o_ch, col->chars, size_t(col->chars_len), hipMemcpyHostToDevice, st));
-        }
-        ea.values = A + o_in;
-        ea.validity = has_val ? A + o_vl : nullptr;
-        ea.offsets = reinterpret_cast<const int32_t*>(A + o_of);
-        ea.chars = A + o_ch;
-    }
-    ea.flag = reinterpret_cast<uint32_t*>(A + o_flag); ea.pos = reinterpret_cast<uint32_t*>(A + o_pos);
-    ea.dense = A + o_dense;
-    ea.dsrc = reinterpret_cast<uint32_t*>(A + o_dsrc); ea.dlen = reinterpret_cast<uint32_t*>(A + o_dlen);
-    ea.vsz = reinterpret_cast<uint32_t*>(A + o_vsz); ea.vpre = reinterpret_cast<uint32_t*>(A + o_vpre);
-    ea.key = reinterpret_cast<uint64_t*>(A + o_key); ea.skey = reinterpret_cast<uint64_t*>(A + o_skey);
-    ea.didx = reinterpret_cast<uint32_t*>(A + o_didx); ea.sidx = reinterpret_cast<uint32_t*>(A + o_sidx);
-    ea.headpos = reinterpret_cast<uint32_t*>(A + o_hp); ea.head = reinterpret_cast<uint32_t*>(A + o_head);
-    ea.mark = reinterpret_cast<uint32_t*>(A + o_mark); ea.did = reinterpret_cast<uint32_t*>(A + o_did);
-    ea.dsz = reinterpret_cast<uint32_t*>(A + o_dsz); ea.doff = reinterpret_cast<uint32_t*>(A + o_doff);
-    ea.ids = reinterpret_cast<uint32_t*>(A + o_ids); ea.collide = reinterpret_cast<uint32_t*>(A + o_col);
-    void* temp = A + o_temp;
-
-    HIPCHK(ctx, hipMemsetAsync(A + o_col, 0, 256, st));
-    if (str) HIPCHK(ctx, hipMemsetAsync(ea.vsz, 0, 4 * N1, st));
-    EVREC(ctx, ctx->ev[2], st);
-    if (n) HIPCHK(ctx, enc_dense(ea, temp, temp_bytes, st));
-    if (str) HIPCHK(ctx, enc_plain_sizes(ea, m, temp, temp_bytes, st));
-    // The device sums dictionary bytes in 32 bits: a BYTE_ARRAY column whose dictionary could reach 4 GiB
-    // (all values distinct: 4 m + chars) is written PLAIN (conservative: such a dictionary is over any
-    // page limit unless most values repeat; parity with parquet-mr's writer is unpinned).
-    const bool dict_fits32 = !str || 4ull * uint64_t(m) + uint64_t(col->chars_len) < (1ull << 32);
-    const bool dict_bit = (col->dictionary & PF_ENCODE_DICTIONARY) != 0;
-    const bool want_dict = dict_bit && pt != PF_BOOLEAN && m > 0 && dict_fits32;
-    uint32_t hres[3] = {0, 0, 0};   // collide, dictionary entries, dictionary bytes
-    float enc_ms = 0.f;
-    if (want_dict) {
-        HIPCHK(ctx, enc_dictionary(ea, m, w == 4 ? 32 : 64, temp, temp_bytes, st));
-        EVREC(ctx, ctx->ev[3], st);
-        HIPCHK(ctx, hipMemcpyAsync(&hres[0], ea.collide, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(&hres[1], ea.did + m, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(&hres[2], ea.doff + m, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&enc_ms, ctx->ev[2], ctx->ev[3]));
-    }
-    int fallback = 0;
-    if (dict_bit && pt == PF_BOOLEAN) fallback = 3;
-    else if (want_dict && hres[0]) fallback = 2;
-    else if (dict_bit && pt != PF_BOOLEAN && m > 0 && !dict_fits32) fallback = 1;
-    else if (want_dict && (str ? int64_t(hres[2]) : int64_t(hres[1]) * w) > dict_limit) fallback = 1;   // fixed: D * w on the host
-    const bool dict = want_dict && fallback == 0;
-    const uint32_t D = dict ? hres[1] : 0, dict_bytes = dict ? (str ? hres[2] : hres[1] * uint32_t(w)) : 0;
-    uint32_t bw = 1;
-    while (D > 1 && (uint64_t(1) << bw) < D) bw++;
-    if (hyb && D == 1) bw = 0;   // parquet-mr's getWidthFromMaxInt(D - 1)
-    const bool brle = hyb && pt == PF_BOOLEAN;   // parquet-mr v2 writes BOOLEAN with the RLE encoding
-
-    // ---- values sections: [dictionary page | page 0 | page 1 | ...] in d_enc_out's front ----
-    const bool delta = delta_bit && !dict;   // the chunk is not dictionary-encoded: DELTA_* pages
-    const int data_enc = dict ? PF_ENC_RLE_DICTIONARY : delta ? (str ? PF_ENC_DELTA_BYTE_ARRAY : PF_ENC_DELTA_BINARY_PACKED)
-                              : brle ? PF_ENC_RLE : PF_ENC_PLAIN;
-    std::vector<EncPage> ep(delta ? 0 : pp.size());
-    std::vector<std::pair<uint64_t, uint64_t>> sections;
-    size_t vo = 0;
-    const size_t o_dict = take(vo, dict_bytes);
-    if (dict) sections.push_back({o_dict, dict_bytes});
-    // Hybrid streams: size pass (after the ids, which it reads) -> the streams' bytes in one D2H and one sync ->
-    // the host sizes the sections and the levels -> write pass over the same grid.
-    std::vector<HybridStream> hs;
-    std::vector<uint32_t> hbytes;
-    std::vector<int> lv_of(pp.size(), -1), vs_of(pp.size(), -1);   // a page's level / value stream
-    std::vector<size_t> lv_off(pp.size(), 0);                       // a page's levels in hlv
-    size_t o_lv = 0, lv_total = 0;
-    HybridArgs ha{};
-    auto hybrid_sizes = [&]() -> int {
-        for (size_t i = 0; i < pp.size() && col->max_def == 1; i++) {
-            lv_of[i] = int(hs.size());
-            hs.push_back(HybridStream{ea.validity, 0, HY_VALIDITY, uint32_t(pp[i].r0), uint32_t(pp[i].r1 - pp[i].r0), 1,
-                                      HY_PREFIX_NONE, uint32_t(i)});
-        }
-        for (size_t i = 0; i < pp.size() && (dict || brle); i++) {
-            vs_of[i] = int(hs.size());
-            hs.push_back(dict ? HybridStream{reinterpret_cast<const uint8_t*>(ea.ids), 0, HY_IDS, pp[i].d0, pp[i].cnt, bw,
-                                             HY_PREFIX_WIDTH, uint32_t(i)}
-                              : HybridStream{ea.dense, 0, HY_BOOL, pp[i].d0, pp[i].cnt, 1, HY_PREFIX_LENGTH, uint32_t(i)});
-        }
-        ha.streams = reinterpret_cast<const HybridStream*>(A + o_hstr);
-        ha.n_streams = uint32_t(hs.size());
-        ha.bytes = reinterpret_cast<uint32_t*>(A + o_hby);
-        hbytes.assign(hs.size(), 0);
-        EVREC(ctx, ctx->ev[6], st);
-        if (dict) enc_dictionary_page_and_ids(ea, m, st);
-        if (!hs.empty()) {
-            HIPCHK(ctx, hipMemcpyAsync(A + o_hstr, hs.data(), sizeof(HybridStream) * hs.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(ctx, enc_hybrid_sizes(ha, st));
-        }
-        EVREC(ctx, ctx->ev[7], st);
-        if (!hs.empty()) HIPCHK(ctx, hipMemcpyAsync(hbytes.data(), ha.bytes, 4 * hs.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (ctx->timing) {
-            float ms = 0.f;
-            HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
-            enc_ms += ms;
-        }
-        return PF_OK;
-    };
-    auto place_levels = [&](size_t& cur) {   // the pages' levels, back to back behind the values sections
-        for (size_t i = 0; i < pp.size(); i++)
-            if (lv_of[i] >= 0) { lv_off[i] = lv_total; lv_total += hbytes[size_t(lv_of[i])]; }
-        o_lv = take(cur, lv_total);
-        for (size_t i = 0; i < pp.size(); i++)
-            if (lv_of[i] >= 0) hs[size_t(lv_of[i])].out_off = o_lv + lv_off[i];
-    };
-    auto hybrid_write = [&](uint8_t* out) -> int {
-        if (hs.empty()) return PF_OK;
-        ha.out = out;
-        HIPCHK(ctx, hipMemcpyAsync(A + o_hstr, hs.data(), sizeof(HybridStream) * hs.size(), hipMemcpyHostToDevice, st));
-        enc_hybrid_write(ha, st);
-        return PF_OK;
-    };
-    // Statistics: the kernels run with the page kernels (their time is in encode_ms), the results come back in
-    // pinned memory with the synchronisation the bodies wait for anyway.
-    const size_t st_bytes = sizeof(StatPart) * n_se + (str ? size_t(ST_LIMIT) * n_se : 0);
-    std::vector<uint32_t> px_in;   // rows of every page, then its present values (alive until the synchronisation: the upload reads it)
-    auto stats_launch = [&]() -> int {
-        if (!run_stats) return PF_OK;
-        StatArgs sa{};
-        sa.tiles = reinterpret_cast<const StatTile*>(A + o_stt); sa.ptile = reinterpret_cast<const uint32_t*>(A + o_stp);
-        sa.n_tiles = uint32_t(stiles.size()); sa.n_pages = uint32_t(pp.size());
-        sa.part = reinterpret_cast<StatPart*>(A + o_spart); sa.win = reinterpret_cast<uint32_t*>(A + o_swin);
-        sa.out = reinterpret_cast<StatPart*>(A + o_sout); sa.bytes = A + o_sbytes;
-        if (!stiles.empty())
-            HIPCHK(ctx, hipMemcpyAsync(A + o_stt, stiles.data(), sizeof(StatTile) * stiles.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(A + o_stp, sptile.data(), 4 * sptile.size(), hipMemcpyHostToDevice, st));
-        enc_stats(ea, sa, st);
-        HIPCHK(ctx, hipGetLastError());
-        if (want_index) {
-            px_in.resize(2 * n_px);
-            for (size_t i = 0; i < n_px; i++) { px_in[i] = uint32_t(pp[i].r1 - pp[i].r0); px_in[n_px + i] = pp[i].cnt; }
-            HIPCHK(ctx, hipMemcpyAsync(A + o_xin, px_in.data(), 8 * n_px, hipMemcpyHostToDevice, st));
-            PgIndexArgs xa{};
-            xa.pages = sa.out;
-            xa.rows = reinterpret_cast<const uint32_t*>(A + o_xin); xa.cnt = xa.rows + n_px;
-            xa.n_pages = uint32_t(n_px); xa.trunc = px_trunc; xa.value_cap = uint32_t(px_cap);
-            xa.nn = reinterpret_cast<uint32_t*>(A + o_xnn);
-            xa.head = reinterpret_cast<PgIndexHead*>(A + o_xout);
-            xa.null_counts = reinterpret_cast<long long*>(A + o_xout + px_nc);
-            xa.off = reinterpret_cast<uint32_t*>(A + o_xout + px_off);
-            xa.null_pages = A + o_xout + px_np;
-            xa.values = A + o_xout + px_val;
-            enc_pgindex(ea, xa, st);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        return PF_OK;
-    };
-    auto stats_fetch = [&]() -> int {
-        if (want_index) {   // one block, in pinned memory, under the synchronisation the bodies wait for
-            HIPCHK(ctx, ctx->h_enc_px.ensure(px_bytes));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_enc_px.p, A + o_xout, px_bytes, hipMemcpyDeviceToHost, st));
-        }
-        if (!want_stats) return PF_OK;
-        HIPCHK(ctx, ctx->h_enc_st.ensure(st_bytes));
-        uint8_t* h = static_cast<uint8_t*>(ctx->h_enc_st.p);
-        HIPCHK(ctx, hipMemcpyAsync(h, A + o_sout, sizeof(StatPart) * n_se, hipMemcpyDeviceToHost, st));
-        if (str) HIPCHK(ctx, hipMemcpyAsync(h + sizeof(StatPart) * n_se, A + o_sbytes, size_t(ST_LIMIT) * n_se, hipMemcpyDeviceToHost, st));
-        return PF_OK;
-    };
-    // Bloom filter (bloom_bytes): zeroed and filled on the stream behind the page kernels, outside encode_ms (events of
-    // its own); the bitset comes back in pinned memory with the copy and synchronisation the bodies wait for anyway.
-    auto bloom_launch = [&]() -> int {
-        if (!bloom) return PF_OK;
-        HIPCHK(ctx, ctx->h_enc_bloom.ensure(bloom));
-        EVREC(ctx, ctx->ev_bloom[0], st);
-        HIPCHK(ctx, hipMemsetAsync(A + o_bloom, 0, bloom, st));
-        enc_bloom(ea, m, reinterpret_cast<uint32_t*>(A + o_bloom), uint32_t(bloom), dict && ctx->opts.bloom_first, st);
-        HIPCHK(ctx, hipGetLastError());
-        EVREC(ctx, ctx->ev_bloom[1], st);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_enc_bloom.p, A + o_bloom, bloom, hipMemcpyDeviceToHost, st));
-        return PF_OK;
-    };
-    if (hyb && delta) {
-        const int rc = hybrid_sizes();
-        if (rc) return rc;
-    }
-    if (delta) {
-        // size pass -> scan -> page totals (one D2H, one sync) -> sections -> write pass
-        DeltaArgs da{};
-        da.streams = reinterpret_cast<const DeltaStream*>(A + o_dstr);
-        da.pages = reinterpret_cast<const DeltaPage*>(A + o_dpg);
-        da.n_streams = uint32_t(dstreams.size() - 1); da.n_pages = uint32_t(dpages.size()); da.n_items = n_items;
-        da.bytes = reinterpret_cast<uint32_t*>(A + o_dby); da.off = reinterpret_cast<uint32_t*>(A + o_dof);
-        da.minv = reinterpret_cast<long long*>(A + o_dmin); da.widths = reinterpret_cast<uint32_t*>(A + o_dwd);
-        da.totals = reinterpret_cast<uint32_t*>(A + o_dtot);
-        if (str) {
-            da.pfx = reinterpret_cast<uint32_t*>(A + o_pfx); da.sfx = reinterpret_cast<uint32_t*>(A + o_sfx);
-            da.spre = reinterpret_cast<uint32_t*>(A + o_spre);
-        }
-        for (size_t s = 0; s + 1 < dstreams.size(); s++) {
-            const DeltaPage& p = dpages[dstreams[s].page];
-            dstreams[s].src = !str ? ea.dense + uint64_t(p.d0) * uint32_t(w)
-                                   : reinterpret_cast<const uint8_t*>((s - p.s0 == 0 ? da.pfx : da.sfx) + p.d0);
-        }
-        EVREC(ctx, ctx->ev[4], st);
-        HIPCHK(ctx, hipMemcpyAsync(A + o_dstr, dstreams.data(), sizeof(DeltaStream) * dstreams.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(A + o_dpg, dpages.data(), sizeof(DeltaPage) * dpages.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemsetAsync(da.bytes + n_items, 0, 4, st));
-        if (str) HIPCHK(ctx, enc_delta_prefix(ea, da, m, temp, temp_bytes, st));
-        HIPCHK(ctx, enc_delta_sizes(da, temp, temp_bytes, st));
-        std::vector<uint32_t> htot(dpages.size());
-        HIPCHK(ctx, hipMemcpyAsync(htot.data(), da.totals, 4 * htot.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        for (size_t i = 0; i < dpages.size(); i++) {
-            if (htot[i] > 0x7fffffffu) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
-            dpages[i].out_off = take(vo, htot[i]);
-            sections.push_back({dpages[i].out_off, htot[i]});
-        }
-        if (hyb) place_levels(vo);
-        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));
-        da.out = static_cast<uint8_t*>(ctx->d_enc_sec.p);
-        HIPCHK(ctx, hipMemcpyAsync(A + o_dpg, dpages.data(), sizeof(DeltaPage) * dpages.size(), hipMemcpyHostToDevice, st));
-        enc_delta_write(ea, da, m, st);
-        if (hyb) {
-            const int rc = hybrid_write(da.out);
-            if (rc) return rc;
-        }
-        HIPCHK(ctx, hipGetLastError());
-        if (const int rc = stats_launch()) return rc;
-        EVREC(ctx, ctx->ev[5], st);
-        if (const int rc = stats_fetch()) return rc;
-        if (const int rc = bloom_launch()) return rc;
-    }
-    uint8_t* SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
-    if (!delta) {   // RLE_DICTIONARY or PLAIN: the host knows every page's size (hybrid runs: after their size pass)
-        if (hyb) {
-            // The dictionary page and the ids are written before the size pass: room for the worst case of
-            // every section (an element is at most a 5-byte varint and the value, or a header and a group)
-            auto worst = [](uint64_t cnt, uint32_t b) { return (cnt / 8 + 1) * std::max<uint64_t>(b + 1, 5 + (b + 7) / 8); };
-            size_t ub = vo + 512 + sizeof(EncPage) * pp.size();
-            for (const PagePlanE& p : pp)
-                ub += 256 + size_t(dict ? 1 + worst(p.cnt, bw) : brle ? 4 + worst(p.cnt, 1) : p.plain) +
-                      size_t(col->max_def == 1 ? worst(uint64_t(p.r1 - p.r0), 1) : 0);
-            HIPCHK(ctx, ctx->d_enc_sec.ensure(ub));
-            ea.dict_out = static_cast<uint8_t*>(ctx->d_enc_sec.p) + o_dict;
-            const int rc = hybrid_sizes();
-            if (rc) return rc;
-        }
-        for (size_t i = 0; i < pp.size(); i++) {
-            const PagePlanE& p = pp[i];
-            uint64_t bytes;
-            if (vs_of[i] >= 0) {   // width byte or 4-byte length, then the stream
-                const uint64_t pre = dict ? 1 : 4;
-                bytes = pre + hbytes[size_t(vs_of[i])];
-                ep[i] = EncPage{0, p.d0, p.cnt, dict ? 1u : 0u, bw};
-                ep[i].out_off = take(vo, bytes);
-                hs[size_t(vs_of[i])].out_off = ep[i].out_off + pre;
-                sections.push_back({ep[i].out_off, bytes});
-                continue;
-            }
-            if (dict) {
-                const uint64_t groups = (p.cnt + 7) / 8;
-                bytes = p.cnt ? 1 + uvarint_len((groups << 1) | 1) + groups * bw : 1;
-            } else {
-                bytes = p.plain;
-            }
-            ep[i] = EncPage{0, p.d0, p.cnt, dict ? 1u : 0u, bw};
-            ep[i].out_off = take(vo, bytes);
-            sections.push_back({ep[i].out_off, bytes});
-        }
-        if (hyb) place_levels(vo);
-        const size_t o_pages = take(vo, sizeof(EncPage) * ep.size());
-        HIPCHK(ctx, ctx->d_enc_sec.ensure(vo));   // hybrid runs: within the worst case reserved above, nothing moves
-        SEC = static_cast<uint8_t*>(ctx->d_enc_sec.p);
-        ea.dict_out = SEC + o_dict;
-        ea.vals_out = SEC;
-        EVREC(ctx, ctx->ev[4], st);
-        if (dict && !hyb) enc_dictionary_page_and_ids(ea, m, st);
-        HIPCHK(ctx, hipMemcpyAsync(SEC + o_pages, ep.data(), sizeof(EncPage) * ep.size(), hipMemcpyHostToDevice, st));
-        if (!(hyb && (dict || brle))) enc_pages(ea, reinterpret_cast<const EncPage*>(SEC + o_pages), int(ep.size()), st);
-        if (hyb) {
-            const int rc = hybrid_write(SEC);
-            if (rc) return rc;
-        }
-        HIPCHK(ctx, hipGetLastError());
-        if (const int rc = stats_launch()) return rc;
-        EVREC(ctx, ctx->ev[5], st);
-        if (const int rc = stats_fetch()) return rc;
-        if (const int rc = bloom_launch()) return rc;
-    }
-    std::vector<std::vector<uint8_t>> bodies;
-    std::vector<uint8_t> hlv(lv_total);   // hybrid runs: the pages' levels
-    float snap_ms = 0.f, crc_ms = 0.f;
-    // Page CRCs (PF_ENCODE_PAGE_CRC): the pieces of the pages that lie in device memory -- the compression jobs'
-    // slots (SNAPPY, ZSTD; compress_sections lists them) or the sections themselves, and the levels: the stream the GPU
-    // encoded (hybrid runs), or the whole validity bytes of the page's rows, which the one bit-packed run repeats
-    // -- go through k_enc_crc; `crcs` holds the jobs (SNAPPY, ZSTD) or sections first, then the levels.
-    std::vector<CrcPiece> lv_pieces;
-    std::vector<CrcOut> crcs;
-    std::vector<int> lv_piece(pp.size(), -1);   // the page's whole level stream
-    std::vector<int> vb_piece(pp.size(), -1);   // the whole bytes of its bit-packed run, between header and last partial byte
-    if (want_crc)
-        for (size_t i = 0; i < pp.size(); i++) {
-            if (lv_of[i] >= 0) {
-                const uint32_t nb = hbytes[size_t(lv_of[i])];
-                lv_piece[i] = int(lv_pieces.size());
-                lv_pieces.push_back(CrcPiece{SEC + o_lv + lv_off[i], nullptr, nb, nb});
-            } else if (has_val && pp[i].r1 - pp[i].r0 >= 8) {   // (pages start on a validity byte)
-                const uint32_t nb = uint32_t((pp[i].r1 - pp[i].r0) / 8);
-                vb_piece[i] = int(lv_pieces.size());
-                lv_pieces.push_back(CrcPiece{ea.validity + pp[i].r0 / 8, nullptr, nb, nb});
-            }
-        }
-    size_t crc_first_lv = 0;   // index of the first level stream in crcs
-    if (compressed) {
-        if (lv_total) HIPCHK(ctx, hipMemcpyAsync(hlv.data(), SEC + o_lv, lv_total, hipMemcpyDeviceToHost, st));
-        const int rc = compress_sections(ctx, SEC, sections, bodies, col->codec, &snap_ms, &lv_pieces, want_crc ? &crcs : nullptr, &crc_ms);
-        if (rc) return rc;
-        if (want_crc) crc_first_lv = crcs.size() - lv_pieces.size();
-    } else {
-        std::vector<CrcPiece> pieces;   // (alive until the synchronisation below: the upload reads it)
-        if (want_crc) {   // the table and the results in d_enc_out, which an uncompressed chunk does not use otherwise
-            for (const auto& sct : sections) {
-                if (sct.second > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "encode: data page over 2 GiB");
-                pieces.push_back(CrcPiece{SEC + sct.first, nullptr, uint32_t(sct.second), uint32_t(sct.second)});
-            }
-            crc_first_lv = pieces.size();
-            pieces.insert(pieces.end(), lv_pieces.begin(), lv_pieces.end());
-            const size_t npc = pieces.size(), o_res = align_up(sizeof(CrcPiece) * npc, 256);
-            HIPCHK(ctx, ctx->d_enc_out.ensure(o_res + sizeof(CrcOut) * npc));
-            uint8_t* d = static_cast<uint8_t*>(ctx->d_enc_out.p);
-            crcs.resize(npc);
-            HIPCHK(ctx, hipMemcpyAsync(d, pieces.data(), sizeof(CrcPiece) * npc, hipMemcpyHostToDevice, st));
-            EVREC(ctx, ctx->ev[8], st);
-            launch_enc_crc(reinterpret_cast<const CrcPiece*>(d), int(npc), reinterpret_cast<CrcOut*>(d + o_res), st);
-            HIPCHK(ctx, hipGetLastError());
-            EVREC(ctx, ctx->ev[9], st);
-            HIPCHK(ctx, hipMemcpyAsync(crcs.data(), d + o_res, sizeof(CrcOut) * npc, hipMemcpyDeviceToHost, st));
-        }
-        std::vector<uint8_t> all(vo);
-        HIPCHK(ctx, hipMemcpyAsync(all.data(), SEC, vo, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (want_crc && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&crc_ms, ctx->ev[8], ctx->ev[9]));
-        if (lv_total) std::memcpy(hlv.data(), all.data() + o_lv, lv_total);
-        for (const auto& sct : sections) bodies.emplace_back(all.begin() + sct.first, all.begin() + sct.first + sct.second);
-    }
-
-    // ---- page headers + bodies ----
-    std::vector<uint8_t>& o = ctx->h_enc;
-    o.clear();
-    int64_t unc = 0;
-    size_t bi = 0;
-    // CRC of a page: its pieces folded in stored order (pf_crc.h); the bytes the host generates itself (the
-    // length varint or the frame header, a bit-packed level run built from hval) are fed bytewise.
-    size_t crc_job = 0;   // SNAPPY, ZSTD: the next job in crcs
-    bool crc_bad = false;
-    auto page_crc = [&](size_t sec, size_t page, const std::vector<uint8_t>& def) {
-        uint32_t raw = 0;
-        uint64_t len = 0;
-        auto piece = [&](const CrcOut& c) { raw = crc_combine_pow(raw, c.raw, c.x8len); len += c.len; };
-        if (page != size_t(-1) && lv_piece[page] >= 0) {
-            piece(crcs[crc_first_lv + size_t(lv_piece[page])]);
-        } else if (page != size_t(-1) && vb_piece[page] >= 0) {   // run header ‖ whole validity bytes (device) ‖ last partial byte
-            const CrcOut& c = crcs[crc_first_lv + size_t(vb_piece[page])];
-            const size_t groups = size_t(pp[page].r1 - pp[page].r0 + 7) / 8, hdr = def.size() - groups;
-            raw = crc_raw_bytes(raw, def.data(), hdr);
-            len += hdr;
-            piece(c);
-            raw = crc_raw_bytes(raw, def.data() + hdr + c.len, def.size() - hdr - c.len);
-            len += def.size() - hdr - c.len;
-        } else {
-            raw = crc_raw_bytes(raw, def.data(), def.size());
-            len += def.size();
-        }
-        if (compressed) {
-            uint8_t head[12];
-            const size_t vl = stream_head(col->codec, sections[sec].second, head);
-            raw = crc_raw_bytes(raw, bodies[sec].data(), vl);
-            len += vl;
-            const uint32_t job = col->codec == PF_CODEC_ZSTD ? ZC_BLOCK : SC_BLOCK;
-            for (uint64_t o = 0; o < sections[sec].second; o += job) piece(crcs[crc_job++]);
-        } else {
-            piece(crcs[sec]);
-        }
-        if (len != def.size() + bodies[sec].size()) crc_bad = true;   // the pieces are not the page
-        return crc_finish(raw, len);
-    };
-    // Statistics of entry e (a page, or pp.size(): the chunk) from the kernels' results
-    const StatPart* hst = want_stats ? static_cast<const StatPart*>(ctx->h_enc_st.p) : nullptr;
-    const uint8_t* hsb = want_stats ? static_cast<const uint8_t*>(ctx->h_enc_st.p) + sizeof(StatPart) * n_se : nullptr;
-    auto stats_of = [&](size_t e, int64_t nulls) {
-        StatsOut so;
-        if (!want_stats || hst[e].any == 2) return so;   // over the size limit: no struct at all
-        so.present = true;
-        so.null_count = nulls;
-        if (hst[e].any != 1) return so;
-        so.has_min_max = true;
-        if (str) {
-            const char* b = reinterpret_cast<const char*>(hsb + e * size_t(ST_LIMIT));
-            so.min.assign(b, hst[e].mnl);
-            so.max.assign(b + hst[e].mnl, hst[e].mxl);
-        } else {   // PLAIN: little-endian, w bytes (BOOLEAN: one byte)
-            so.min.assign(reinterpret_cast<const char*>(&hst[e].mn), size_t(w));
-            so.max.assign(reinterpret_cast<const char*>(&hst[e].mx), size_t(w));
-        }
-        so.legacy = !str || so.min == so.max;   // parquet-mr: the legacy fields only where the signed order is the type's
-        return so;
-    };
-    out->dictionary_page_offset = -1;
-    if (dict) {
-        PageHeaderOut h;
-        h.page_type = PF_PAGE_DICTIONARY;
-        h.uncompressed_size = int32_t(dict_bytes);
-        h.compressed_size = int32_t(bodies[0].size());
-        h.num_values = int32_t(D);
-        h.encoding = PF_ENC_PLAIN;   // parquet-mr PARQUET_2_0: dictionary page PLAIN, data pages RLE_DICTIONARY
-        if (want_crc) { h.has_crc = true; h.crc = page_crc(0, size_t(-1), {}); }
-        out->dictionary_page_offset = 0;
-        const size_t h0 = o.size();
-        write_page_header(o, h);
-        unc += int64_t(o.size() - h0) + dict_bytes;
-        o.insert(o.end(), bodies[0].begin(), bodies[0].end());
-        bi = 1;
-    }
-    out->data_page_offset = int64_t(o.size());
-    ctx->h_enc_pgoff.assign(n_px, 0);
-    ctx->h_enc_pgrow.assign(n_px, 0);
-    ctx->h_enc_pgsize.assign(n_px, 0);
-    for (size_t i = 0; i < pp.size(); i++, bi++) {
-        const PagePlanE& p = pp[i];
-        const int64_t rows = p.r1 - p.r0;
-        std::vector<uint8_t> def;
-        if (lv_of[i] >= 0) {       // hybrid runs: the stream the GPU encoded from the validity bits
-            def.assign(hlv.begin() + lv_off[i], hlv.begin() + lv_off[i] + hbytes[size_t(lv_of[i])]);
-        } else if (col->max_def == 1) {   // RLE/bit-packed hybrid, bit width 1: one bit-packed run = the validity bits
-            const uint64_t groups = uint64_t(rows + 7) / 8;
-            put_uvarint(def, (groups << 1) | 1);
-            for (uint64_t g = 0; g < groups; g++) {
-                uint8_t b = has_val ? hval[size_t(p.r0 / 8 + g)] : 0xff;
-                const int64_t left = rows - int64_t(g) * 8;
-                if (left < 8) b &= uint8_t((1u << left) - 1u);
-                def.push_back(b);
-            }
-            if (rows == 0) def.clear();
-        }
-        PageHeaderOut h;
-        h.page_type = PF_PAGE_DATA_V2;
-        h.uncompressed_size = int32_t(def.size() + sections[bi].second);
-        h.compressed_size = int32_t(def.size() + bodies[bi].size());
-        h.num_values = int32_t(rows);
-        h.num_nulls = int32_t(rows - p.cnt);
-        h.num_rows = int32_t(rows);
-        h.encoding = data_enc;
-        h.def_bytes = int32_t(def.size());
-        h.is_compressed = compressed;
-        if (want_crc) { h.has_crc = true; h.crc = page_crc(bi, i, def); }
-        h.stats = stats_of(i, rows - p.cnt);
-        const size_t h0 = o.size();
-        write_page_header(o, h);
-        unc += int64_t(o.size() - h0) + h.uncompressed_size;
-        o.insert(o.end(), def.begin(), def.end());
-        o.insert(o.end(), bodies[bi].begin(), bodies[bi].end());
-        if (want_index) {   // the OffsetIndex entry: the host knows where it put the page
-            ctx->h_enc_pgoff[i] = int64_t(h0);
-            ctx->h_enc_pgsize[i] = int32_t(o.size() - h0);
-            ctx->h_enc_pgrow[i] = p.r0;
-        }
-    }
-    if (crc_bad) return fail(ctx, PF_ERR_HIP, "encode: the CRC pieces of a page do not add up to its size");
-    out->stats_flags = 0;
-    out->stat_min_len = out->stat_max_len = 0;
-    out->null_count = 0;
-    out->stat_min = out->stat_max = nullptr;
-    if (want_stats) {
-        const StatsOut so = stats_of(pp.size(), n - int64_t(m));
-        std::vector<uint8_t>& hb = ctx->h_enc_stat;
-        hb.assign(so.min.begin(), so.min.end());
-        hb.insert(hb.end(), so.max.begin(), so.max.end());
-        hb.push_back(0);   // never empty: the pointers below are not null
-        if (so.present) { out->stats_flags |= PF_STATS_NULL_COUNT; out->null_count = so.null_count; }
-        if (so.has_min_max) {
-            out->stats_flags |= PF_STATS_MIN_MAX;
-            out->stat_min_len = int32_t(so.min.size());
-            out->stat_max_len = int32_t(so.max.size());
-            out->stat_min = hb.data();
-            out->stat_max = hb.data() + so.min.size();
-        }
-    }
-    out->bytes = o.data();
-    out->size = int64_t(o.size());
-    out->total_uncompressed_size = unc;
-    out->num_values = n;
-    out->n_data_pages = int32_t(pp.size());
-    out->dict_entries = int32_t(D);
-    out->data_encoding = data_enc;
-    out->fallback = fallback;
-    out->codec = col->codec;
-    if (ctx->timing) {   // the page kernels' events have completed (the stream was synchronised since)
-        float pg_ms = 0.f;
-        HIPCHK(ctx, hipEventElapsedTime(&pg_ms, ctx->ev[4], ctx->ev[5]));
-        enc_ms += pg_ms + crc_ms;
-    }
-    out->snappy_ms = snap_ms;
-    out->encode_ms = enc_ms;
-    out->bloom = bloom ? static_cast<const uint8_t*>(ctx->h_enc_bloom.p) : nullptr;
-    out->bloom_len = int32_t(bloom);
-    out->bloom_ms = 0.f;
-    if (bloom && ctx->timing) HIPCHK(ctx, hipEventElapsedTime(&out->bloom_ms, ctx->ev_bloom[0], ctx->ev_bloom[1]));
-    out->index_pages = 0;
-    out->page_offset = nullptr; out->page_size = nullptr; out->page_first_row = nullptr;
-    out->column_index = 0; out->boundary_order = 0;
-    out->index_null_pages = nullptr; out->index_null_counts = nullptr;
-    out->index_values = nullptr; out->index_value_off = nullptr;
-    if (want_index) {
-        const uint8_t* h = static_cast<const uint8_t*>(ctx->h_enc_px.p);
-        const PgIndexHead* hd = reinterpret_cast<const PgIndexHead*>(h);
-        if (hd->value_bytes > px_cap && hd->valid) return fail(ctx, PF_ERR_HIP, "encode: the page index values exceed their block");
-        out->index_pages = int32_t(n_px);
-        out->page_offset = ctx->h_enc_pgoff.data();
-        out->page_size = ctx->h_enc_pgsize.data();
-        out->page_first_row = ctx->h_enc_pgrow.data();
-        out->column_index = hd->valid ? 1 : 0;
-        out->boundary_order = hd->valid ? int32_t(hd->order) : 0;
-        out->index_null_pages = h + px_np;
-        out->index_null_counts = reinterpret_cast<const int64_t*>(h + px_nc);
-        if (hd->valid) {
-            out->index_values = h + px_val;
-            out->index_value_off = reinterpret_cast<const uint32_t*>(h + px_off);
-        }
-    }
-    out->snappy_in = 0;
-    out->snappy_out = 0;
-    if (compressed)
-        for (size_t i = 0; i < sections.size(); i++) {
-            out->snappy_in += int64_t(sections[i].second);
-            out->snappy_out += int64_t(bodies[i].size());
-        }
-    return PF_OK;
-}
+// The write path (pf_encode_chunk, pf_snappy_compress, pf_zstd_compress) is pf_enc_runtime.hip, planned by pf_enc_plan.cpp.
 
 extern "C" {
 

@@ -287,7 +287,7 @@ def expand(stream, tokens):
 # wave compresses one job of JOB input bytes on its own, and a page's stream is the preamble followed by
 # its jobs' outputs, so the tokens of job j are those whose output starts in [j * JOB, (j + 1) * JOB).
 
-JOB = 8192          # SC_BLOCK (pf_encode.h)
+JOB = 8192          # SC_BLOCK (pf_enc_tables.h)
 
 
 def job_bound(n):

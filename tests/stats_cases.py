@@ -9,7 +9,7 @@ import numpy as np
 
 import pagekit as K
 
-TILE = 4096          # ST_TILE of csrc/pf_encode.h: dense values of one workgroup (test_write_stats_cpu.py pins it)
+TILE = 4096          # ST_TILE of csrc/pf_enc_tables.h: dense values of one workgroup (test_write_stats_cpu.py pins it)
 LIMIT = 4096         # len(min) + len(max) at or above it: no Statistics struct
 DEFAULT_PAGE_ROWS = 20000
 _FMT = {K.INT32: "<i", K.INT64: "<q", K.FLOAT: "<f", K.DOUBLE: "<d"}

@@ -358,3 +358,57 @@ def test_write_config4_shape(dec, oracle, tmp_path):
             assert np.array_equal(np.unpackbits(g["validity"], bitorder="little")[:n].astype(bool), present)
     t = pq.read_table(path)
     assert t.column("c0").null_count == int((~exp[0][1]).sum())
+
+
+def test_rejected_calls_leave_the_context_usable(dec):
+    """Three calls the host planner (csrc/pf_enc_plan.cpp) rejects return their status code and pf_last_error text;
+    afterwards the same context encodes an OPTIONAL INT32 and a BYTE_ARRAY chunk (dictionary, statistics, page
+    CRCs, page index) to the bytes a fresh context gives."""
+    import ctypes as C
+    from pfloor import writer as W
+    from pfloor._native import lib
+    from pfloor.decoder import GpuDecoder
+    n = 16
+    vals = (np.arange(n, dtype=np.int32) * 7) % 5
+    validity = np.packbits(np.arange(n) % 3 != 0, bitorder="little")
+    words = [b"w%d" % (i % 4) for i in range(n)]
+    offs = np.zeros(n + 1, np.int32)
+    np.cumsum([len(x) for x in words], out=offs[1:])
+    chars = np.frombuffer(b"".join(words), np.uint8)
+
+    def column(**kw):
+        c = W.EncodeColumn()
+        c.physical_type, c.max_def, c.num_rows, c.codec, c.dictionary = W.INT32, 0, n, W.SNAPPY, 1
+        c.values = vals.ctypes.data
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    bad_offs = offs.copy()
+    bad_offs[5] = bad_offs[4] - 1
+    rejected = [
+        (column(bloom_bytes=48), -1, "encode: bloom_bytes must be a power of two in [32, 128 MiB]"),
+        (column(physical_type=W.BINARY, values=None, offsets=bad_offs.ctypes.data, chars=chars.ctypes.data,
+                chars_len=chars.size), -1, "encode: offsets out of order or outside chars"),
+        (column(max_def=2), -1, "encode: bad shape"),
+    ]
+    for c, code, text in rejected:
+        out = W.EncodedChunk()
+        assert lib().pf_encode_chunk(dec.h, C.byref(c), 0, C.byref(out)) == code
+        assert dec.error() == text
+
+    def encode_both(d):
+        enc = W.GpuColumnEncoder(d)
+        kw = dict(dictionary=True, statistics=True, page_checksums=True, page_index=True)
+        a = enc.encode(W.optional(W.INT32).named("v"), vals, validity, n, **kw)
+        a = C.string_at(a.bytes, a.size)
+        b = enc.encode(W.required(W.BINARY).named("s"), (offs, chars), None, n, **kw)
+        return a, C.string_at(b.bytes, b.size)
+
+    fresh = GpuDecoder(0)
+    try:
+        expect = encode_both(fresh)
+    finally:
+        fresh.close()
+    got = encode_both(dec)
+    assert got == expect and len(got[0]) > 0 and len(got[1]) > 0

@@ -28,7 +28,7 @@ def W():
 def test_constants_are_the_headers(W):
     hdr = open(os.path.join(ROOT, "include", "pfloor.h")).read()
     assert int(re.search(r"#define PF_ENCODE_PAGE_INDEX\s+(\d+)", hdr).group(1)) == W.ENCODE_PAGE_INDEX == 32
-    src = open(os.path.join(CSRC, "pf_encode.h")).read()
+    src = open(os.path.join(CSRC, "pf_enc_tables.h")).read()
     assert int(re.search(r"ST_LIMIT = (\d+);", src).group(1)) == P.LIMIT
     assert (W.UNORDERED, W.ASCENDING, W.DESCENDING) == (P.UNORDERED, P.ASCENDING, P.DESCENDING) == (0, 1, 2)
 

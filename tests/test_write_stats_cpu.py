@@ -27,7 +27,7 @@ def W():
 
 def test_tile_size_is_the_kernels():
     """The page sizes of the GPU cases sit around ST_TILE and the size limit is ST_LIMIT."""
-    src = open(os.path.join(CSRC, "pf_encode.h")).read()
+    src = open(os.path.join(CSRC, "pf_enc_tables.h")).read()
     assert int(re.search(r"ST_TILE = (\d+);", src).group(1)) == S.TILE
     assert int(re.search(r"ST_LIMIT = (\d+);", src).group(1)) == S.LIMIT
     hdr = open(os.path.join(ROOT, "include", "pfloor.h")).read()

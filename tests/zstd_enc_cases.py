@@ -9,7 +9,7 @@ import numpy as np
 
 import zstd_frames as Z
 
-JOB = 8192                      # ZC_BLOCK (pf_encode.h)
+JOB = 8192                      # ZC_BLOCK (pf_enc_tables.h)
 CUTS = (0, 1, 2, 3, 4, 5, 8191, 8192, 8193, 16384, 65537)
 
 
