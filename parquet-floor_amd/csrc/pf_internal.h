@@ -52,6 +52,7 @@ struct PfOpts {
     bool nest_seg_set = false;
     bool dbp_par = true;      // PF_DBP_PAR=0: every DELTA_BINARY_PACKED page on k_delta
     bool bloom_first = true;  // PF_BLOOM_FIRST=0: a dictionary-encoded chunk's Bloom filter hashes every value, not the first occurrences
+    bool flat_dstr = true;    // PF_FLAT_DSTR=0: k_flat_dstr takes no page (k_flat_all decodes the small-dictionary string pages)
     int fix_shift = 1;        // PF_FIX_BLK=4096|8192|16384: fixed-width flat blocks (log2 of the multiple of 4096)
 };
 
@@ -134,7 +135,8 @@ PF_HD inline uint32_t zstd_lit_stride(uint32_t max_dst) {
 
 // DONE_PAGE: k_page_null decoded the whole page (with DONE_NULL); k_lvl and k_flat_null skip only
 // such pages -- never DONE_NULL itself, which k_flat_null's own finished blocks of the page set.
-enum : int32_t { DONE_FIXED = 1, DONE_FLAT = 2, DONE_NULL = 4, DONE_PAGE = 8 };
+// DONE_DSTR: k_flat_dstr decoded the page (set together with DONE_FLAT); k_flat_all's blocks of the page return at it.
+enum : int32_t { DONE_FIXED = 1, DONE_FLAT = 2, DONE_NULL = 4, DONE_PAGE = 8, DONE_DSTR = 16 };
 
 // DevPage.direct (k_snappy_head): how the page's decompressed body reaches the decoders
 enum : int32_t { DIRECT_NONE = 0, DIRECT_VALUES = 1, DIRECT_INPLACE = 2 };

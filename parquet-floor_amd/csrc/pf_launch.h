@@ -38,7 +38,7 @@ void launch_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, i
 void launch_count_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_flat, const int2* d_dblk,
                        int n_dblk, DevChunkResult* d_res, BaJob* d_bajobs, hipStream_t st);
 void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
-                 DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
+                 const int2* d_dblk, int n_dblk, DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
 
 // pf_decode.hip
 void launch_nest_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int max_nwin, DevChunkResult* d_res,

@@ -186,7 +186,8 @@ int enqueue_kernels(pf_ctx* ctx) {
     EVREC(ctx, ctx->ev[8], st);
     if (!(skip & 32u))
         launch_flat(d_chunks, d_pages, list(L_FLAT), p.n_flat_fixed, p.n_flat_all, p.n_null4, p.n_null8,
-                    reinterpret_cast<int*>(meta + p.off_nfbq), d_res, st, ncaps, ctx->opts.null_stagger);
+                    reinterpret_cast<int*>(meta + p.off_nfbq), pairs(L_CDICT), ctx->opts.flat_dstr ? len(L_CDICT) / 2 : 0, d_res, st,
+                    ncaps, ctx->opts.null_stagger);
     EVREC(ctx, ctx->ev[9], st);
     if (!(skip & 64u)) launch_decode(d_chunks, d_pages, list(L_DECODE), len(L_DECODE), p.n_decode_first, d_res, st, DECODE_IDLE_GRID);
     launch_nest_decode(d_chunks, d_pages, pairs(L_NSEG), n_nseg, d_res, st);
@@ -361,6 +362,7 @@ void opts_from_env(pf::PfOpts& o) {
     }
     o.dbp_par = on("PF_DBP_PAR", o.dbp_par);
     o.bloom_first = on("PF_BLOOM_FIRST", o.bloom_first);
+    o.flat_dstr = on("PF_FLAT_DSTR", o.flat_dstr);
     const int fb = num("PF_FIX_BLK", 8192);
     o.fix_shift = fb >= 16384 ? 2 : (fb >= 8192 ? 1 : 0);
 }
@@ -1329,7 +1331,7 @@ int pf_debug_page_paths(pf_ctx* ctx, int* out, int n_pages) {
 }
 
 // Diagnostics (tests): the done flags of the last decode's pages (DONE_FIXED 1 / DONE_FLAT 2 /
-// DONE_NULL 4: which kernel took the page; k_page_null and k_flat_null both set DONE_NULL, and only
+// DONE_NULL 4 / DONE_DSTR 16 with DONE_FLAT: which kernel took the page; k_page_null and k_flat_null both set DONE_NULL, and only
 // k_page_null's pages keep no level table (lvl = 0 in out[2 * i + 1])).
 extern "C" int pf_debug_page_done(pf_ctx* ctx, int* out, int n_pages) {
     std::vector<DevPage> pg;
