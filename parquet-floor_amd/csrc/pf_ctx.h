@@ -12,6 +12,7 @@
 
 #include "pf_launch.h"
 #include "pf_plan.h"
+#include "pf_result.h"
 #include "pfloor.h"
 
 namespace pf {
@@ -121,6 +122,12 @@ struct pf_ctx {
     pf::DevBuf d_win, d_wout, d_wbits, d_wchars;
     pf::HostBuf h_win;                     // DevWin[n] up, DevWinRes[n] down
     int win_grid = 1;
+    // this batch's side-table layouts (pf_result.h), each computed once in enqueue_batch and read by enqueue_kernels
+    // and pf_wait; the twin deltas from where the arenas were bound
+    pf::ResLayout res_lay{};
+    pf::WinLayout win_lay{};
+    pf::SelLayout sel_lay;
+    pf::TwinDelta twin;
     hipEvent_t ev_win[2] = {};
     // row filter (pf_decode_row_group_filter): the packed predicates (none: no filter stage), the stage's device buffer
     // and its pinned mirror: [DevSelHead | DevSelChunk[n]] comes down, [DevPred[] | blob | win_of[n]] goes up
@@ -128,8 +135,6 @@ struct pf_ctx {
     pf::DevBuf d_sel;
     pf::HostBuf h_sel;
     pf::SelBufs sel{};
-    size_t sel_up_off = 0;                 // where the uploaded tables begin: the bytes before them come down
-    int sel_grid = 1;
     hipEvent_t ev_sel[2] = {};
     pf_selection_info sel_info{};
     bool filtered() const { return !filt.preds.empty(); }

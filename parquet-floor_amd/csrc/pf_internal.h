@@ -373,6 +373,24 @@ struct DevSelHead {
     int32_t status;           // a predicate chunk's failure (every chunk takes it), or rows_in out of range
     int32_t pad;
 };
+// The filter stage's device buffers (one context buffer, sized from the host's row counts: layout_filter, pf_result.h).
+// rows_cap bounds rows_in; tiles_cap = the tiles of rows_cap, also the stride of ba_sum / ba_base (one row per chunk).
+struct SelBufs {
+    DevSelHead* head;
+    DevSelChunk* sc;          // [n_chunks]
+    const DevPred* preds;     // [n_preds], then the blob of BYTE_ARRAY bounds
+    const uint8_t* blob;
+    const int32_t* win_of;    // [n_chunks]: the chunk's entry in the window tables, -1 without one
+    uint64_t* mask;           // [tiles_cap * SEL_TILE / 64]
+    uint32_t* tile_count;     // [tiles_cap] selected rows per tile, and their exclusive scan
+    uint32_t* tile_base;
+    int32_t* rows;            // [rows_cap] the selected row numbers (16-byte aligned)
+    uint32_t* ba_sum;         // [n_chunks * tiles_cap] chars per output tile, and their exclusive scan
+    uint32_t* ba_base;
+    int64_t* ba_total;        // [n_chunks]
+    int64_t rows_cap, tiles_cap;
+    int32_t n_preds;
+};
 
 // GPU page-header scan (pf_scan.hip, pf_scan_pages)
 struct ScanChunk {            // device copy of pf_scan_chunk

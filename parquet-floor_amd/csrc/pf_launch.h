@@ -65,24 +65,7 @@ void launch_window(const DevChunk* d_chunks, const DevChunkResult* d_res, const 
                    int copy_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
                    hipStream_t st);
 
-// pf_filter.hip: the filter stage's device buffers (one context buffer, sized from the host's row counts) and its launch.
-// rows_cap bounds rows_in; tiles_cap = the tiles of rows_cap, also the stride of ba_sum / ba_base (one row per chunk).
-struct SelBufs {
-    DevSelHead* head;
-    DevSelChunk* sc;          // [n_chunks]
-    const DevPred* preds;     // [n_preds], then the blob of BYTE_ARRAY bounds
-    const uint8_t* blob;
-    const int32_t* win_of;    // [n_chunks]: the chunk's entry in the window tables, -1 without one
-    uint64_t* mask;           // [tiles_cap * SEL_TILE / 64]
-    uint32_t* tile_count;     // [tiles_cap] selected rows per tile, and their exclusive scan
-    uint32_t* tile_base;
-    int32_t* rows;            // [rows_cap] the selected row numbers (16-byte aligned)
-    uint32_t* ba_sum;         // [n_chunks * tiles_cap] chars per output tile, and their exclusive scan
-    uint32_t* ba_base;
-    int64_t* ba_total;        // [n_chunks]
-    int64_t rows_cap, tiles_cap;
-    int32_t n_preds;
-};
+// pf_filter.hip: the filter stage's launch (SelBufs: pf_internal.h, laid out and bound by pf_result.cpp)
 void launch_filter(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWinRes* d_wres, const SelBufs& f, int n_chunks,
                    int gather_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
                    hipStream_t st);

@@ -6,8 +6,9 @@
 // SnappyJob tables, launch lists and arena sizes; this file grows the arenas to those sizes, has
 // the planner bind its offsets to them, uploads the tables in one copy, and enqueues
 //   k_snappy / k_zstd -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
-// on the context stream. Nothing synchronises until pf_wait. The context itself is pf_ctx.h; the write path
-// is a unit of its own, pf_enc_runtime.hip.
+// on the context stream. Nothing synchronises until pf_wait, which hands what came down to the host-only result
+// side (pf_result.cpp: side-table layouts, the rerun decision, pf_column_info). The context itself is pf_ctx.h; the
+// write path is a unit of its own, pf_enc_runtime.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -193,41 +194,33 @@ int enqueue_kernels(pf_ctx* ctx) {
     launch_nest_decode(d_chunks, d_pages, pairs(L_NSEG), n_nseg, d_res, st);
     launch_dba_chars(d_chunks, d_pages, list(L_DBA), len(L_DBA), d_res, st);
     EVREC(ctx, ctx->ev[10], st);
-    if (!ctx->wins.empty()) {   // row windows: after every decode stage, so a chars rerun trims again
-        const int nw = int(ctx->wins.size());
-        const size_t res_off = align_up(sizeof(DevWin) * nw, 256);
-        DevWin* d_wins = static_cast<DevWin*>(ctx->d_win.p);
-        DevWinRes* d_wres = reinterpret_cast<DevWinRes*>(static_cast<uint8_t*>(ctx->d_win.p) + res_off);
+    const WinLayout& wl = ctx->win_lay;
+    const bool windowed = !ctx->wins.empty();
+    DevWinRes* d_wres = windowed ? reinterpret_cast<DevWinRes*>(static_cast<uint8_t*>(ctx->d_win.p) + wl.res_off) : nullptr;
+    if (windowed) {   // row windows: after every decode stage, so a chars rerun trims again
         EVREC(ctx, ctx->ev_win[0], st);
-        launch_window(d_chunks, d_res, d_wins, d_wres, nw, ctx->win_grid, static_cast<const uint8_t*>(ctx->d_chars.p),
-                      static_cast<uint8_t*>(ctx->d_wchars.p),
-                      static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p),
-                      static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p), st);
+        launch_window(d_chunks, d_res, static_cast<DevWin*>(ctx->d_win.p), d_wres, int(ctx->wins.size()), ctx->win_grid,
+                      static_cast<const uint8_t*>(ctx->d_chars.p), static_cast<uint8_t*>(ctx->d_wchars.p), ctx->twin.out,
+                      ctx->twin.bits, st);
         EVREC(ctx, ctx->ev_win[1], st);
-        HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_win.p) + res_off, d_wres, sizeof(DevWinRes) * nw,
-                                   hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_win.p) + wl.res_off, d_wres, wl.res_bytes, hipMemcpyDeviceToHost, st));
     }
     if (ctx->filtered()) {   // the row filter: after the windows, so it sees their rows and a chars rerun filters again
-        const DevWinRes* d_wres = ctx->wins.empty() ? nullptr : reinterpret_cast<const DevWinRes*>(
-            static_cast<const uint8_t*>(ctx->d_win.p) + align_up(sizeof(DevWin) * ctx->wins.size(), 256));
         EVREC(ctx, ctx->ev_sel[0], st);
-        launch_filter(d_chunks, d_res, d_wres, ctx->sel, ctx->n_chunks, ctx->sel_grid, static_cast<const uint8_t*>(ctx->d_chars.p),
-                      static_cast<uint8_t*>(ctx->d_wchars.p),
-                      static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p),
-                      static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p), st);
+        launch_filter(d_chunks, d_res, d_wres, ctx->sel, ctx->n_chunks, ctx->sel_lay.grid, static_cast<const uint8_t*>(ctx->d_chars.p),
+                      static_cast<uint8_t*>(ctx->d_wchars.p), ctx->twin.out, ctx->twin.bits, st);
         EVREC(ctx, ctx->ev_sel[1], st);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_sel.p, ctx->d_sel.p, ctx->sel_up_off, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_sel.p, ctx->d_sel.p, ctx->sel_lay.o_up, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipGetLastError());
     // results + device-written chunk fields (chars base) back to pinned host memory
-    const size_t res_pad = align_up(sizeof(DevChunkResult) * ctx->n_chunks, 256);
+    const ResLayout& rl = ctx->res_lay;
     if (ctx->zc && ctx->h_res.d) {
-        copy_words(ctx->h_res.d, meta + p.off_res, sizeof(DevChunkResult) * ctx->n_chunks,
-                   static_cast<uint8_t*>(ctx->h_res.d) + res_pad, d_chunks, sizeof(DevChunk) * ctx->n_chunks, st);
+        copy_words(ctx->h_res.d, meta + p.off_res, rl.res_bytes, static_cast<uint8_t*>(ctx->h_res.d) + rl.chunks_off, d_chunks,
+                   rl.chunks_bytes, st);
     } else {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_res.p, meta + p.off_res, sizeof(DevChunkResult) * ctx->n_chunks,
-                                   hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_res.p) + res_pad, d_chunks, sizeof(DevChunk) * ctx->n_chunks,
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_res.p, meta + p.off_res, rl.res_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_res.p) + rl.chunks_off, d_chunks, rl.chunks_bytes,
                                    hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_done, st));
@@ -492,55 +485,16 @@ int pf_memcpy_h2d(pf_ctx* ctx, void* dst, const void* src, size_t bytes) {
 }  // extern "C"
 
 namespace {
-// The filter stage's buffer for the planned batch: sized from the host's row counts, its tables uploaded.
+// The filter stage's buffer for the planned batch (laid out by layout_filter), its tables uploaded.
 int bind_filter(pf_ctx* ctx) {
-    const BatchPlan& p = ctx->plan;
-    const FilterPlan& f = ctx->filt;
-    const size_t nc = size_t(ctx->n_chunks), np = f.preds.size();
-    std::vector<int32_t> win_of(nc, -1);
-    for (size_t i = 0; i < ctx->wins.size(); i++) win_of[size_t(ctx->wins[i].chunk)] = int32_t(i);
-    // rows_in is the first predicate chunk's row count after its window: at most take rows, or the chunk's entries
-    // (a predicate chunk is flat: rows = entries)
-    const int c0 = f.preds[0].chunk;
-    int64_t rows_cap = p.chunks[size_t(c0)].num_entries;
-    if (win_of[size_t(c0)] >= 0 && ctx->wins[size_t(win_of[size_t(c0)])].take >= 0)
-        rows_cap = std::min<int64_t>(rows_cap, ctx->wins[size_t(win_of[size_t(c0)])].take);
-    rows_cap = std::max<int64_t>(rows_cap, 0);
-    const size_t tiles = std::max<size_t>(1, (size_t(rows_cap) + SEL_TILE - 1) / SEL_TILE);
-    size_t m = 0;
-    auto take = [&](size_t n) { const size_t o = align_up(m, 256); m = o + n; return o; };
-    const size_t o_head = take(sizeof(DevSelHead)), o_sc = take(sizeof(DevSelChunk) * nc);
-    const size_t o_up = take(0), o_preds = take(sizeof(DevPred) * np), o_blob = take(f.blob.size()), o_winof = take(4 * nc);
-    const size_t up_end = m;
-    const size_t o_mask = take(8 * tiles * (SEL_TILE / 64)), o_tc = take(4 * tiles), o_tb = take(4 * tiles);
-    const size_t o_rows = take(4 * tiles * SEL_TILE), o_bs = take(4 * tiles * nc), o_bb = take(4 * tiles * nc), o_bt = take(8 * nc);
-    HIPCHK(ctx, ctx->d_sel.ensure(m));
-    HIPCHK(ctx, ctx->h_sel.ensure(up_end));
+    const SelLayout& l = ctx->sel_lay = layout_filter(ctx->plan, ctx->filt, ctx->wins);
+    HIPCHK(ctx, ctx->d_sel.ensure(l.total));
+    HIPCHK(ctx, ctx->h_sel.ensure(l.up_end));
     uint8_t* h = static_cast<uint8_t*>(ctx->h_sel.p);
-    uint8_t* d = static_cast<uint8_t*>(ctx->d_sel.p);
-    std::memset(h, 0, up_end);
-    std::memcpy(h + o_preds, f.preds.data(), sizeof(DevPred) * np);
-    if (!f.blob.empty()) std::memcpy(h + o_blob, f.blob.data(), f.blob.size());
-    std::memcpy(h + o_winof, win_of.data(), 4 * nc);
-    HIPCHK(ctx, hipMemcpyAsync(d + o_up, h + o_up, up_end - o_up, hipMemcpyHostToDevice, ctx->stream));
-    SelBufs& s = ctx->sel;
-    s.head = reinterpret_cast<DevSelHead*>(d + o_head);
-    s.sc = reinterpret_cast<DevSelChunk*>(d + o_sc);
-    s.preds = reinterpret_cast<const DevPred*>(d + o_preds);
-    s.blob = d + o_blob;
-    s.win_of = reinterpret_cast<const int32_t*>(d + o_winof);
-    s.mask = reinterpret_cast<uint64_t*>(d + o_mask);
-    s.tile_count = reinterpret_cast<uint32_t*>(d + o_tc);
-    s.tile_base = reinterpret_cast<uint32_t*>(d + o_tb);
-    s.rows = reinterpret_cast<int32_t*>(d + o_rows);
-    s.ba_sum = reinterpret_cast<uint32_t*>(d + o_bs);
-    s.ba_base = reinterpret_cast<uint32_t*>(d + o_bb);
-    s.ba_total = reinterpret_cast<int64_t*>(d + o_bt);
-    s.rows_cap = rows_cap;
-    s.tiles_cap = int64_t(tiles);
-    s.n_preds = int32_t(np);
-    ctx->sel_up_off = o_up;
-    ctx->sel_grid = int(std::min<size_t>(tiles, 256));
+    fill_filter(l, ctx->filt, h);
+    HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->d_sel.p) + l.o_up, h + l.o_up, l.up_end - l.o_up, hipMemcpyHostToDevice,
+                               ctx->stream));
+    ctx->sel = bind_sel(l, ctx->filt, reinterpret_cast<uintptr_t>(ctx->d_sel.p));
     return PF_OK;
 }
 
@@ -576,40 +530,34 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     plan_batch(cds, n_chunks, n_bytes, ctx->opts, p);
     mark();
     // ---- arenas ----
-    const size_t chars_cap = std::max<size_t>(size_t(2 * p.chars_hint) + (16u << 20), ctx->chars_need);
-    // (the window kernels read validity bits in 8-byte words: room for the last one)
-    const size_t bits_cap = std::max<size_t>(p.bits_bytes, 1) + (twins ? 8 : 0);
+    const ArenaNeeds need = arena_needs(p, ctx->chars_need, twins);
     if (ctx->copies_pending) {
-        if (p.out_bytes > ctx->d_out.cap || bits_cap > ctx->d_bits.cap || chars_cap > ctx->d_chars.cap ||
-            (twins && (ctx->d_out.cap > ctx->d_wout.cap || ctx->d_bits.cap > ctx->d_wbits.cap || ctx->d_chars.cap > ctx->d_wchars.cap)))
+        if (arenas_grow(need, ArenaCaps{ctx->d_out.cap, ctx->d_bits.cap, ctx->d_chars.cap, ctx->d_wout.cap, ctx->d_wbits.cap,
+                                        ctx->d_wchars.cap}, twins))
             HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // a growing output arena must not be freed under a pending D2H copy
         else
             HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_copy, 0));   // (a download on the copy stream reads the arenas)
     }
     ctx->copies_pending = false;
     HIPCHK(ctx, ctx->d_scratch.ensure(std::max<size_t>(p.scratch_bytes, 1)));
-    HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(p.out_bytes, 1)));
-    HIPCHK(ctx, ctx->d_bits.ensure(bits_cap));
-    HIPCHK(ctx, ctx->d_chars.ensure(chars_cap));
+    HIPCHK(ctx, ctx->d_out.ensure(std::max<size_t>(need.out, 1)));
+    HIPCHK(ctx, ctx->d_bits.ensure(need.bits));
+    HIPCHK(ctx, ctx->d_chars.ensure(need.chars));
+    ctx->twin = TwinDelta{};
     if (twins) {   // the twins: the decode arenas' sizes, so a chunk keeps its offsets
         HIPCHK(ctx, ctx->d_wout.ensure(ctx->d_out.cap));
         HIPCHK(ctx, ctx->d_wbits.ensure(ctx->d_bits.cap));
         HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
+        ctx->twin.out = static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p);
+        ctx->twin.bits = static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p);
     }
     if (windowed) {
-        const int nw = int(ctx->wins.size());
-        const size_t tab = align_up(sizeof(DevWin) * nw, 256) + sizeof(DevWinRes) * nw;
-        HIPCHK(ctx, ctx->d_win.ensure(tab));
-        HIPCHK(ctx, ctx->h_win.ensure(tab));
-        std::memcpy(ctx->h_win.p, ctx->wins.data(), sizeof(DevWin) * nw);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win.p, ctx->h_win.p, sizeof(DevWin) * nw, hipMemcpyHostToDevice, st));
-        uint64_t tiles = 1;   // k_win_copy's workgroups per chunk stride over its tiles: a bound from the host's counts
-        for (const DevWin& w : ctx->wins) {
-            const DevChunk& ck = p.chunks[size_t(w.chunk)];
-            const uint64_t n = ck.max_rep == 0 && w.take >= 0 ? uint64_t(w.take) : uint64_t(ck.num_entries);
-            tiles = std::max<uint64_t>(tiles, n * uint64_t(std::max(ck.width, 8)) / WIN_TILE + 8);
-        }
-        ctx->win_grid = int(std::min<uint64_t>(tiles, 512));
+        const WinLayout& wl = ctx->win_lay = win_layout(int(ctx->wins.size()));
+        HIPCHK(ctx, ctx->d_win.ensure(wl.total));
+        HIPCHK(ctx, ctx->h_win.ensure(wl.total));
+        std::memcpy(ctx->h_win.p, ctx->wins.data(), wl.wins_bytes);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win.p, ctx->h_win.p, wl.wins_bytes, hipMemcpyHostToDevice, st));
+        ctx->win_grid = win_grid(p, ctx->wins);
     }
     if (ctx->filtered()) {
         const int rc = bind_filter(ctx);
@@ -618,7 +566,8 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     HIPCHK(ctx, ctx->d_tokmap.ensure(p.snap.tokmap_bytes));
     HIPCHK(ctx, ctx->d_meta.ensure(p.meta_bytes));
     HIPCHK(ctx, ctx->h_meta.ensure(p.meta_bytes));
-    HIPCHK(ctx, ctx->h_res.ensure(align_up(sizeof(DevChunkResult) * n_chunks, 256) + sizeof(DevChunk) * n_chunks + 256));
+    ctx->res_lay = res_layout(n_chunks);
+    HIPCHK(ctx, ctx->h_res.ensure(ctx->res_lay.total));
     mark();
     auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
     bind_batch(p, ArenaBases{addr(d_bytes), addr(ctx->d_scratch.p), addr(ctx->d_out.p), addr(ctx->d_bits.p), addr(ctx->d_meta.p),
@@ -742,20 +691,13 @@ int pf_wait(pf_ctx* ctx) {
     for (;;) {
         hipError_t e = hipEventSynchronize(ctx->ev_done);
         if (e != hipSuccess) { ctx->pending = false; return fail(ctx, PF_ERR_HIP, std::string("decode: ") + hipGetErrorString(e)); }
-        const DevChunkResult* r = static_cast<const DevChunkResult*>(ctx->h_res.p);
-        const DevChunk* dc = reinterpret_cast<const DevChunk*>(static_cast<uint8_t*>(ctx->h_res.p) +
-                                                               align_up(sizeof(DevChunkResult) * ctx->n_chunks, 256));
+        const uint8_t* hres = static_cast<const uint8_t*>(ctx->h_res.p);
+        const DevChunkResult* r = reinterpret_cast<const DevChunkResult*>(hres);
         // chars arena overflow: grow to the exact need and run the batch once more
-        uint64_t need = 0;
-        bool overflow = false;
-        for (int c = 0; c < ctx->n_chunks; c++) {
-            if (ctx->plan.chunks[c].ptype == PF_BYTE_ARRAY) need += align_up(uint64_t(std::max<int64_t>(r[c].num_chars, 0)), 256);
-            if (r[c].status == PF_ERR_CAPACITY && ctx->plan.chunks[c].ptype == PF_BYTE_ARRAY && r[c].num_chars <= 0x7fffffff)
-                overflow = true;
-        }
-        if (overflow && ctx->reruns == 0) {
+        const CharsOverflow ov = chars_overflow(ctx->plan, r);
+        if (ov.rerun && ctx->reruns == 0) {
             ctx->reruns++;
-            ctx->chars_need = size_t(need) + (1u << 20);
+            ctx->chars_need = size_t(ov.need) + (1u << 20);
             HIPCHK(ctx, ctx->d_chars.ensure(ctx->chars_need));
             if (ctx->twins()) HIPCHK(ctx, ctx->d_wchars.ensure(ctx->d_chars.cap));
             int rc = upload_meta(ctx);
@@ -764,82 +706,24 @@ int pf_wait(pf_ctx* ctx) {
             if (rc) { ctx->pending = false; return rc; }
             continue;
         }
-        int first_err = PF_OK;
-        size_t wi = 0;
-        const DevWinRes* wr = ctx->wins.empty() ? nullptr : reinterpret_cast<const DevWinRes*>(
-            static_cast<const uint8_t*>(ctx->h_win.p) + align_up(sizeof(DevWin) * ctx->wins.size(), 256));
-        for (int c = 0; c < ctx->n_chunks; c++) {
-            pf_column_info& ci = ctx->info[c];
-            const DevChunk& ck = ctx->plan.chunks[c];
-            ci.num_entries = ck.num_entries;
-            ci.num_slots = r[c].num_slots;
-            ci.num_values = r[c].num_values;
-            ci.num_rows = r[c].num_rows;
-            ci.num_chars = ck.ptype == PF_BYTE_ARRAY ? r[c].num_chars : 0;
-            ci.width = ck.width;
-            ci.status = r[c].status;
-            ci.d_values = ck.values;
-            ci.d_validity = ck.validity;
-            ci.d_offsets = ck.offsets;
-            ci.d_chars = dc[c].chars;
-            ci.d_list_offsets = ck.list_offsets;
-            ci.d_list_validity = ck.list_validity;
-            ci.d_def_levels = ck.def_levels;
-            ci.d_rep_levels = ck.rep_levels;
-            if (wi < ctx->wins.size() && ctx->wins[wi].chunk == c) {   // the window's view (chunks ascend in wins)
-                const DevWinRes& w = wr[wi++];
-                if (ci.status == 0 && w.status != 0) ci.status = w.status;
-                else if (ci.status == 0 && !w.identity) {
-                    const ptrdiff_t od = static_cast<uint8_t*>(ctx->d_wout.p) - static_cast<uint8_t*>(ctx->d_out.p);
-                    const ptrdiff_t bd = static_cast<uint8_t*>(ctx->d_wbits.p) - static_cast<uint8_t*>(ctx->d_bits.p);
-                    auto tw = [](auto* q, ptrdiff_t d) { return q ? reinterpret_cast<decltype(q)>(reinterpret_cast<uint8_t*>(q) + d) : nullptr; };
-                    ci.num_entries = w.n_entries;
-                    ci.num_slots = w.n_slots;
-                    ci.num_values = w.n_values;
-                    ci.num_rows = w.n_rows;
-                    ci.num_chars = ck.ptype == PF_BYTE_ARRAY ? w.n_chars : 0;
-                    ci.d_values = tw(ck.values, od);
-                    ci.d_validity = tw(ck.validity, bd);
-                    ci.d_offsets = tw(ck.offsets, od);
-                    ci.d_chars = w.chars_dst;
-                    ci.d_list_offsets = tw(ck.list_offsets, od);
-                    ci.d_list_validity = tw(ck.list_validity, bd);
-                    ci.d_def_levels = tw(ck.def_levels, od);
-                    ci.d_rep_levels = tw(ck.rep_levels, od);
-                }
-            }
-            if (ctx->filtered()) {   // the selection's view
-                const DevSelHead& sh = *static_cast<const DevSelHead*>(ctx->h_sel.p);
-                const DevSelChunk& sc = reinterpret_cast<const DevSelChunk*>(static_cast<const uint8_t*>(ctx->h_sel.p) +
-                                                                            align_up(sizeof(DevSelHead), 256))[c];
-                if (ci.status == 0 && sc.status != 0) ci.status = sc.status;   // (its own, or a predicate chunk's)
-                else if (ci.status == 0) {
-                    ci.num_entries = ci.num_slots = ci.num_rows = sh.rows_selected;
-                    ci.num_values = sc.n_values;
-                    ci.num_chars = ck.ptype == PF_BYTE_ARRAY ? sc.n_chars : 0;
-                    ci.d_values = sc.o_values;
-                    ci.d_validity = sc.o_validity;
-                    ci.d_offsets = sc.o_offsets;
-                    ci.d_chars = sc.o_chars;
-                }
-                if (c == 0) {
-                    ctx->sel_info = pf_selection_info{};
-                    ctx->sel_info.rows_in = sh.rows_in;
-                    ctx->sel_info.rows_selected = sh.rows_selected;
-                    ctx->sel_info.d_rows = ctx->sel.rows;
-                    ctx->sel_info.status = sh.status;
-                }
-            }
-            if (ci.status != 0 && first_err == PF_OK) {
-                first_err = ci.status;
-                char buf[160];
-                std::snprintf(buf, sizeof buf, "chunk %d: decode failed (status %d, page %d)", c, ci.status, r[c].err_page);
-                fail(ctx, first_err, buf);
-            }
-        }
+        const uint8_t* hwin = static_cast<const uint8_t*>(ctx->h_win.p);
+        const uint8_t* hsel = static_cast<const uint8_t*>(ctx->h_sel.p);
+        const bool filtered = ctx->filtered();
+        BatchResults br{};
+        br.res = r;
+        br.dev_chunks = reinterpret_cast<const DevChunk*>(hres + ctx->res_lay.chunks_off);
+        br.wins = ctx->wins.data();
+        br.n_wins = ctx->wins.size();
+        br.wres = br.n_wins ? reinterpret_cast<const DevWinRes*>(hwin + ctx->win_lay.res_off) : nullptr;
+        br.twin = ctx->twin;
+        br.sel_head = filtered ? reinterpret_cast<const DevSelHead*>(hsel + ctx->sel_lay.o_head) : nullptr;
+        br.sel_chunks = filtered ? reinterpret_cast<const DevSelChunk*>(hsel + ctx->sel_lay.o_sc) : nullptr;
+        br.sel_rows = ctx->sel.rows;
+        const FirstError fe = assemble_info(ctx->plan, br, ctx->info.data(), &ctx->sel_info);
+        if (fe.code != PF_OK) fail(ctx, fe.code, fe.msg);
         ctx->pending = false;
         ctx->timing_valid = true;
-        return first_err;
+        return fe.code;
     }
 }
 
@@ -852,29 +736,26 @@ int pf_column_info_get(pf_ctx* ctx, int chunk, pf_column_info* out) {
 }
 
 namespace {
-// Enqueue the D2H copies of chunk i's arrays on the context stream (no synchronisation).
-int enqueue_copy(pf_ctx* ctx, int chunk, const pf_column_out* o) {
+// Chunk i's arrays against the caller's buffers: the call's checks, capacities last (nothing is enqueued).
+int check_copy(pf_ctx* ctx, int chunk, const pf_column_out* o, CopyItem items[8]) {
     if (!ctx || !o) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
     const pf_column_info& ci = ctx->info[chunk];
     if (ci.status != 0) return fail(ctx, ci.status, "chunk failed to decode");
-    struct Item { void* dst; size_t cap; const void* src; size_t n; };
-    Item items[8] = {
-        {o->values, o->values_cap, ci.d_values, size_t(ci.num_slots) * size_t(ci.width)},
-        {o->validity, o->validity_cap, ci.d_validity, size_t((ci.num_slots + 7) / 8)},
-        {o->offsets, o->offsets_cap, ci.d_offsets, ci.d_offsets ? 4 * size_t(ci.num_slots + 1) : 0},
-        {o->chars, o->chars_cap, ci.d_chars, size_t(ci.num_chars)},
-        {o->list_offsets, o->list_offsets_cap, ci.d_list_offsets, ci.d_list_offsets ? 4 * size_t(ci.num_rows + 1) : 0},
-        {o->list_validity, o->list_validity_cap, ci.d_list_validity, size_t((ci.num_rows + 7) / 8)},
-        {o->def_levels, o->def_levels_cap, ci.d_def_levels, size_t(ci.num_entries)},
-        {o->rep_levels, o->rep_levels_cap, ci.d_rep_levels, size_t(ci.num_entries)},
-    };
-    for (const Item& it : items)
-        if (it.dst && it.src && it.n > it.cap) return fail(ctx, PF_ERR_CAPACITY, "output buffer too small");
+    copy_items(ci, *o, items);
+    for (int k = 0; k < 8; k++)
+        if (items[k].wanted() && items[k].n > items[k].cap) return fail(ctx, PF_ERR_CAPACITY, "output buffer too small");
+    return PF_OK;
+}
+// Enqueue the D2H copies of chunk i's arrays on the context stream (no synchronisation).
+int enqueue_copy(pf_ctx* ctx, int chunk, const pf_column_out* o) {
+    CopyItem items[8];
+    const int rc = check_copy(ctx, chunk, o, items);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (const Item& it : items)
-        if (it.dst && it.src && it.n) HIPCHK(ctx, hipMemcpyAsync(it.dst, it.src, it.n, hipMemcpyDeviceToHost, ctx->stream));
+    for (const CopyItem& it : items)
+        if (it.wanted() && it.n) HIPCHK(ctx, hipMemcpyAsync(it.dst, it.src, it.n, hipMemcpyDeviceToHost, ctx->stream));
     return PF_OK;
 }
 }  // namespace
@@ -890,24 +771,9 @@ int pf_copy_column(pf_ctx* ctx, int chunk, const pf_column_out* o) {
 int pf_copy_columns_async(pf_ctx* ctx, int n, const int* chunks, const pf_column_out* outs) {
     if (!ctx || n < 0 || (n > 0 && (!chunks || !outs))) return fail(ctx, PF_ERR_INVALID_ARG, "bad arguments");
     for (int i = 0; i < n; i++) {   // capacities first: nothing is enqueued if any buffer is too small
-        if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
-        const int c = chunks[i];
-        if (c < 0 || c >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
-        const pf_column_info& ci = ctx->info[c];
-        if (ci.status != 0) return fail(ctx, ci.status, "chunk failed to decode");
-        const pf_column_out& o = outs[i];
-        const size_t need[8] = {size_t(ci.num_slots) * size_t(ci.width), size_t((ci.num_slots + 7) / 8),
-                                ci.d_offsets ? 4 * size_t(ci.num_slots + 1) : 0, size_t(ci.num_chars),
-                                ci.d_list_offsets ? 4 * size_t(ci.num_rows + 1) : 0, size_t((ci.num_rows + 7) / 8),
-                                size_t(ci.num_entries), size_t(ci.num_entries)};
-        const void* dst[8] = {o.values, o.validity, o.offsets, o.chars, o.list_offsets, o.list_validity, o.def_levels,
-                              o.rep_levels};
-        const void* src[8] = {ci.d_values, ci.d_validity, ci.d_offsets, ci.d_chars, ci.d_list_offsets, ci.d_list_validity,
-                              ci.d_def_levels, ci.d_rep_levels};
-        const size_t cap[8] = {o.values_cap, o.validity_cap, o.offsets_cap, o.chars_cap, o.list_offsets_cap,
-                               o.list_validity_cap, o.def_levels_cap, o.rep_levels_cap};
-        for (int k = 0; k < 8; k++)
-            if (dst[k] && src[k] && need[k] > cap[k]) return fail(ctx, PF_ERR_CAPACITY, "output buffer too small");
+        CopyItem items[8];
+        const int rc = check_copy(ctx, chunks[i], &outs[i], items);
+        if (rc) return rc;
     }
     for (int i = 0; i < n; i++) {
         const int rc = enqueue_copy(ctx, chunks[i], &outs[i]);
@@ -921,28 +787,8 @@ int pf_copy_columns_async(pf_ctx* ctx, int n, const int* chunks, const pf_column
 }
 
 namespace {
-// Host layout of pf_copy_batch_async: [out arena | bits arena | chars arena], each 256-B aligned.
-struct BatchLayout { size_t out, bits_off, bits, chars_off, chars, total; };
-BatchLayout batch_layout(const pf_ctx* ctx) {
-    BatchLayout b{};
-    b.out = ctx->plan.out_bytes;
-    b.bits_off = align_up(b.out, 256);
-    b.bits = ctx->plan.bits_bytes;
-    b.chars_off = align_up(b.bits_off + b.bits, 256);
-    const uint8_t* c0 = static_cast<const uint8_t*>(ctx->d_chars.p);
-    size_t hi = 0, bound = 0;
-    for (int c = 0; c < ctx->n_chunks && c < int(ctx->info.size()); c++) {
-        const pf_column_info& ci = ctx->info[c];
-        if (ci.d_chars && ci.num_chars > 0) {
-            hi = std::max(hi, size_t(static_cast<const uint8_t*>(ci.d_chars) - c0) + size_t(ci.num_chars));
-            bound += align_up(size_t(ci.num_chars), 256);
-        }
-    }
-    b.chars = hi;   // bytes copied: the arena's used extent (depends on the order k_scan placed the chunks)
-    // buffer size: an order-independent bound, so equal batches always need equal buffers
-    b.total = b.chars_off + std::max(hi, bound);
-    return b;
-}
+// Host layout of pf_copy_batch_async for the last decode (pf_result.h).
+BatchLayout last_layout(const pf_ctx* ctx) { return batch_layout(ctx->plan, ctx->info, ctx->d_chars.p); }
 }  // namespace
 
 int pf_batch_bytes(pf_ctx* ctx, size_t* bytes) {
@@ -950,7 +796,7 @@ int pf_batch_bytes(pf_ctx* ctx, size_t* bytes) {
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
     if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
-    *bytes = batch_layout(ctx).total;
+    *bytes = last_layout(ctx).total;
     return PF_OK;
 }
 
@@ -959,7 +805,7 @@ int pf_copy_batch_async(pf_ctx* ctx, void* host, size_t cap) {
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (!ctx->tables_from_decode) return fail(ctx, PF_ERR_STATE, "no finished decode");
     if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
-    const BatchLayout b = batch_layout(ctx);
+    const BatchLayout b = last_layout(ctx);
     if (b.total > cap) return fail(ctx, PF_ERR_CAPACITY, "batch buffer too small (pf_batch_bytes)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     uint8_t* h = static_cast<uint8_t*>(host);
@@ -1009,29 +855,7 @@ int pf_column_info_host(pf_ctx* ctx, int chunk, const void* host, pf_column_info
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
     if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
     if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
-    const BatchLayout b = batch_layout(ctx);
-    const uint8_t* h = static_cast<const uint8_t*>(host);
-    auto rebase = [&](const void* p) -> const void* {
-        if (!p) return nullptr;
-        const uint8_t* q = static_cast<const uint8_t*>(p);
-        const uint8_t* o = static_cast<const uint8_t*>(ctx->d_out.p);
-        const uint8_t* v = static_cast<const uint8_t*>(ctx->d_bits.p);
-        const uint8_t* c = static_cast<const uint8_t*>(ctx->d_chars.p);
-        if (q >= o && q <= o + b.out) return h + (q - o);
-        if (q >= v && q <= v + b.bits) return h + b.bits_off + (q - v);
-        if (q >= c && q <= c + b.chars) return h + b.chars_off + (q - c);
-        return nullptr;
-    };
-    pf_column_info ci = ctx->info[chunk];
-    ci.d_values = rebase(ci.d_values);
-    ci.d_validity = static_cast<const uint8_t*>(rebase(ci.d_validity));
-    ci.d_offsets = static_cast<const int32_t*>(rebase(ci.d_offsets));
-    ci.d_chars = static_cast<const uint8_t*>(rebase(ci.d_chars));
-    ci.d_list_offsets = static_cast<const int32_t*>(rebase(ci.d_list_offsets));
-    ci.d_list_validity = static_cast<const uint8_t*>(rebase(ci.d_list_validity));
-    ci.d_def_levels = static_cast<const uint8_t*>(rebase(ci.d_def_levels));
-    ci.d_rep_levels = static_cast<const uint8_t*>(rebase(ci.d_rep_levels));
-    *out = ci;
+    *out = rebase_info(last_layout(ctx), ArenaPtrs{ctx->d_out.p, ctx->d_bits.p, ctx->d_chars.p}, host, ctx->info[chunk]);
     return PF_OK;
 }
 
@@ -1043,6 +867,22 @@ int pf_sync(pf_ctx* ctx) {
     ctx->copies_pending = false;
     return PF_OK;
 }
+
+namespace {
+// The head of a one-shot call (Snappy, ZSTD, page scan): the arenas may be reallocated below, so this context's pending
+// copies out of them finish first. drop_batch: d_meta will hold this call's layout, the last decode's tables are gone.
+int begin_oneshot(pf_ctx* ctx, bool drop_batch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
+    ctx->copies_pending = false;
+    if (drop_batch) {
+        ctx->n_chunks = 0;
+        ctx->info.clear();
+        ctx->tables_from_decode = false;
+    }
+    return PF_OK;
+}
+}  // namespace
 
 int pf_snappy_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len) {
     if (!ctx || (!src && n) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
@@ -1058,13 +898,8 @@ int pf_snappy_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst
     *out_len = size_t(ulen);
     if (ulen > cap) return fail(ctx, PF_ERR_CAPACITY, "snappy: destination too small");
     if (n > 0xffffffffull || ulen > 0xffffffffull) return fail(ctx, PF_ERR_INVALID_ARG, "snappy: buffer too large");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = begin_oneshot(ctx, true)) return rc;
     hipStream_t st = ctx->stream;
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // arenas may be reallocated below
-    ctx->copies_pending = false;
-    ctx->n_chunks = 0;
-    ctx->info.clear();
-    ctx->tables_from_decode = false;   // d_meta now holds this call's layout
     HIPCHK(ctx, ctx->d_in.ensure(std::max<size_t>(n, 1)));
     HIPCHK(ctx, ctx->d_scratch.ensure(std::max<size_t>(ulen, 1) + 16));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_in.p, src, n, hipMemcpyHostToDevice, st));
@@ -1119,13 +954,8 @@ int pf_zstd_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, 
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
     if (n > (1ull << 30) || cap > (1ull << 30)) return fail(ctx, PF_ERR_INVALID_ARG, "zstd: buffer too large");
     *out_len = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = begin_oneshot(ctx, true)) return rc;
     hipStream_t st = ctx->stream;
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));   // arenas may be reallocated below
-    ctx->copies_pending = false;
-    ctx->n_chunks = 0;
-    ctx->info.clear();
-    ctx->tables_from_decode = false;   // d_meta now holds this call's layout
     const uint32_t stride = zstd_lit_stride(uint32_t(cap));
     const size_t o_lit = align_up(cap + 16, 256);
     HIPCHK(ctx, ctx->d_in.ensure(std::max<size_t>(n, 1)));
@@ -1175,10 +1005,8 @@ int pf_scan_pages(pf_ctx* ctx, const pf_scan_chunk* chunks, int n_chunks, const 
         slots = std::max<int64_t>(slots, int64_t(k.page_base) + k.page_cap);
     }
     if (slots > (int64_t(1) << 30)) return fail(ctx, PF_ERR_INVALID_ARG, "scan: too many page slots");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = begin_oneshot(ctx, false)) return rc;   // (its tables are d_scan's: the last decode's stay)
     hipStream_t st = ctx->stream;
-    if (ctx->copies_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
-    ctx->copies_pending = false;
     const uint8_t* d_bytes = bytes;
     if (!bytes_on_device && n_bytes) {
         HIPCHK(ctx, ctx->d_scan_in.ensure(n_bytes));
