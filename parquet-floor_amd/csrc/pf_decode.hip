@@ -115,7 +115,7 @@ __device__ void count_page(const DevChunk* __restrict__ chunks, DevPage* pages, 
         // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY: lengths decoded by k_dlen (pf_delta.hip)
         if (threadIdx.x == 0) {
             if (int64_t(vals) > pg.dx_total || int64_t(vals) > pg.dx_bad) verr = 1;
-            else chars_acc = pg.dx[vals];
+            else chars_acc = dx_cpos(pg.dx)[vals];
         }
         __syncthreads();
         if (verr) { if (threadIdx.x == 0) set_status(res, pg.chunk, ST_CORRUPT, pi); return; }
@@ -413,8 +413,9 @@ __device__ __forceinline__ void decode_page(const DevChunk* __restrict__ chunks,
                         if (int64_t(id) < ck.dict_n) { my_src[k] = ck.dict_pos[id]; my_len[k] = ck.dict_len[id]; }
                         else S.verr = 1;
                     } else if (enc == 6 || enc == 7) {   // cpos: chars before value gv (checked by k_count)
-                        my_src[k] = uint64_t(pg.dx_data) + pg.dx[gv];
-                        my_len[k] = uint32_t(pg.dx[gv + 1] - pg.dx[gv]);
+                        const uint64_t* cpos = dx_cpos(pg.dx);
+                        my_src[k] = uint64_t(pg.dx_data) + cpos[gv];
+                        my_len[k] = uint32_t(cpos[gv + 1] - cpos[gv]);
                     } else {
                         uint32_t p = pg.aux[gv];
                         uint32_t l = (p >= 4 && p <= s.val_n) ? ld32le(s.val, p - 4, s.val_n) : 0xffffffffu;

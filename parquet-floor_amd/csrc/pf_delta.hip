@@ -253,7 +253,7 @@ __global__ __launch_bounds__(DP_NT) void k_dbp_pos(const DevChunk* __restrict__ 
     const DbpHdr H = dbp_header(p, n, ck.ptype == 2, uint64_t(pg.aux_cap));
     if (!H.ok || H.nblocks == 0 || H.nblocks > pg.dbp_bcap) { if (w == 0 && tid == 0) dbp_fail(pg); return; }
     if (w == 0 && tid == 0) __hip_atomic_fetch_max(&pg.dbp_ok, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t* bpos = reinterpret_cast<uint32_t*>(pg.dbp);
+    uint32_t* bpos = dbp_tabs(pg.dbp, pg.dbp_bcap).pos;
     const uint64_t w0 = H.pos0 + uint64_t(w) * DBP_WIN, w1 = w0 + DBP_WIN;
     if (w0 >= n && w > 0) return;
     const bool last = w1 >= n;
@@ -350,8 +350,7 @@ __global__ __launch_bounds__(DP_NT) void k_dbp_blk(const DevChunk* __restrict__ 
 
 // one block, one wave (k_dbp_blk); false after a failed check
 __device__ bool dbp_block(DevPage& pg, const uint8_t* p, uint64_t n, const DbpHdr& H, bool is64, uint64_t b, int lane, int mode) {
-    const uint32_t* bpos = reinterpret_cast<const uint32_t*>(pg.dbp);
-    uint64_t* bsum = reinterpret_cast<uint64_t*>(pg.dbp + 4ull * pg.dbp_bcap + 8 - ((4ull * pg.dbp_bcap) & 7));
+    const auto [bpos, bsum] = dbp_tabs(pg.dbp, pg.dbp_bcap);
     uint64_t pos = bpos[b], md;
     if (!uvarint(p, n, pos, md)) { if (lane == 0) dbp_fail(pg); return false; }
     int64_t mind = unzigzag(md);
@@ -412,7 +411,7 @@ __global__ __launch_bounds__(DP_NT) void k_dbp_scan(const DevChunk* __restrict__
     uint64_t n;
     values_section(pg, ck, p, n);
     const DbpHdr H = dbp_header(p, n, ck.ptype == 2, uint64_t(pg.aux_cap));
-    uint64_t* bsum = reinterpret_cast<uint64_t*>(pg.dbp + 4ull * pg.dbp_bcap + 8 - ((4ull * pg.dbp_bcap) & 7));
+    uint64_t* bsum = dbp_tabs(pg.dbp, pg.dbp_bcap).sum;
     if (threadIdx.x == 0 && H.total > 0) reinterpret_cast<uint64_t*>(pg.aux)[0] = H.first;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     uint64_t carry = H.first;
@@ -484,9 +483,9 @@ __global__ __launch_bounds__(DNT) void k_dlen(const DevChunk* __restrict__ chunk
     const uint8_t* p;
     uint64_t n;
     const uint64_t cap = uint64_t(pg.aux_cap);
-    uint64_t* cpos = pg.dx;
-    uint64_t* la = cpos + cap + 1;
-    uint64_t* lb = la + cap;
+    uint64_t* cpos = dx_cpos(pg.dx);
+    uint64_t* la = dx_len_a(pg.dx, cap);
+    uint64_t* lb = dx_len_b(pg.dx, cap);
     uint64_t t1 = 0, e1 = 0, t2 = 0, e2 = 0;
     bool ok = values_section(pg, ck, p, n);
     if (ok) ok = dbp_decode_wg(S, p, n, false, la, cap, false, t1, e1);
@@ -563,9 +562,9 @@ __global__ __launch_bounds__(64) void k_dba_chars(const DevChunk* __restrict__ c
     if (!values_section(pg, ck, p, n)) return;   // k_dlen reported it
     const uint64_t nv = uint64_t(pg.n_values);
     const uint64_t cap = uint64_t(pg.aux_cap);
-    const uint64_t* cpos = pg.dx;
-    const uint64_t* la = cpos + cap + 1;
-    const uint64_t* lb = la + cap;
+    const uint64_t* cpos = dx_cpos(pg.dx);
+    const uint64_t* la = dx_len_a(pg.dx, cap);
+    const uint64_t* lb = dx_len_b(pg.dx, cap);
     const uint8_t* sfx = p + pg.dx_data;
     const uint64_t sfx_n = n - pg.dx_data;
     const uint64_t w = flba ? uint64_t(ck.width) : 0;

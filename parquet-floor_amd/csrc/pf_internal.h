@@ -11,12 +11,7 @@
 #pragma once
 #include <stdint.h>
 
-// The host planner (pf_plan.cpp) includes this header from plain C++
-#ifdef __HIPCC__
-#define PF_HD __host__ __device__
-#else
-#define PF_HD
-#endif
+#include "pf_page_tables.h"   // PF_HD, FBLK and the per-page side tables
 
 namespace pf {
 
@@ -57,7 +52,6 @@ struct PfOpts {
 };
 
 // Numbers the host planner sizes tables by and the kernels index them by
-constexpr uint32_t FBLK = 4096;            // entries per (page, block) pair of the flat kernels
 constexpr uint32_t BA_TILE = 8192;         // stream bytes per PLAIN BYTE_ARRAY walk tile (k_ba_*)
 // k_ba_tile links values of up to ~124 bytes within a tile; pages of longer values would all take
 // the exact fallback walk there, so a batch with a walk whose values average more than BA_SHORT
@@ -165,17 +159,17 @@ struct DevPage {
     int64_t value_start;
     int64_t row_start;
     int64_t char_start;
-    // per-page scratch: BYTE_ARRAY value positions (PLAIN) or dictionary ids
+    // per-page scratch: BYTE_ARRAY value positions (PLAIN) or dictionary ids, then the block chars (block_chars)
     uint32_t* aux;
     int64_t aux_cap;          // entries
     int32_t ba_job;           // PLAIN BYTE_ARRAY data page: its BaJob (k_count fills it), else -1
     int32_t counted;          // 1: k_count_flat counted the page (k_count skips it)
-    uint32_t* runtab;         // dictionary data page of a flat chunk: id run table (k_runs), else null
-    uint32_t* lvltab;         // nullable fixed-width page of a flat chunk: definition-level run table (k_lvl), else null
+    IdRunTab* runtab;         // dictionary data page of a flat chunk: id run table (k_runs), else null
+    LvlHead* lvltab;          // nullable fixed-width page of a flat chunk: definition-level run table (k_lvl), else null
     uint32_t lvl_cap;         // runs the level table can hold
-    // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY page (k_dlen, pf_delta.hip): {cpos[aux_cap + 1],
-    // lenA[aux_cap], lenB[aux_cap]} (u64), values in the length streams, first bad value, and
-    // where the chars / suffixes start in the values section; else null
+    // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY page (k_dlen, pf_delta.hip): the length tables (dx_cpos,
+    // dx_len_a, dx_len_b), values in the length streams, first bad value, and where the chars / suffixes
+    // start in the values section; else null
     uint64_t* dx;
     int64_t dx_total;
     int64_t dx_bad;
@@ -197,8 +191,8 @@ struct DevPage {
     int32_t seg_ok;           // k_nest_lvl: 1 = the segment kernels decode the page (k_count / k_decode skip it)
     int32_t nwin;             // k_nest_lvl windows per level stream (the page's bytes / NEST_WIN, rounded up)
     struct WinPub* npub;      // [2][nwin]: what each window of the rep / def stream passes to the next (zeroed per batch)
-    // large DELTA_BINARY_PACKED INT32 / INT64 pages decoded block-parallel (k_dbp_*, pf_delta.hip), else null:
-    // {uint32_t pos[dbp_bcap] (block header positions), uint64_t sum[dbp_bcap] (block delta sums, then bases)}
+    // large DELTA_BINARY_PACKED INT32 / INT64 pages decoded block-parallel (k_dbp_*, pf_delta.hip): the block
+    // tables (dbp_tabs), else null
     uint8_t* dbp;
     struct WinPub* dbp_pub;   // [dbp_nwin] window hand-overs of the block chain (zeroed per batch)
     int32_t dbp_nwin;
@@ -239,34 +233,6 @@ constexpr uint32_t NEST_SEG = 2048;         // default entries per segment
 constexpr uint32_t NEST_MAX_SEGS = 1024;    // segments per page (k_nest_scan keeps their targets in LDS)
 PF_HD inline uint64_t nest_seg_bytes(int32_t nseg) {
     return uint64_t(nseg) * (3ull * NEST_CK_BYTES + sizeof(SegRec));
-}
-
-// k_runs run table of a page: {nruns, values covered, all levels present, valid}, then nruns
-// entries {first | packed << 31, RLE value or bit offset}; a run's count is the next first - first.
-constexpr uint32_t RT_CAP = 1024;
-constexpr uint32_t RT_BYTES = 16 + 8 * RT_CAP;
-
-// k_lvl definition-level run table of a nullable flat page: {nruns, valid, present values, -}, then
-// nruns entries {first entry, RLE value or bit offset, count | packed << 31, present values before},
-// then LT_BT_WORDS words per 4096-entry block (k_flat_null): {first run, end run, first value index,
-// end value index, level bytes [d0, d1), dictionary-id bytes [i0, i1)} of the block.
-constexpr uint32_t LT_BLOCK_RUNS = 512;    // most runs one k_flat_null block may overlap (its LDS table)
-constexpr uint32_t LT_BT_WORDS = 8;
-constexpr uint32_t NL_DST = 4096;          // most level bytes one k_flat_null block stages in LDS
-constexpr uint32_t NULL_DICT_LDS = 16384;   // k_flat_null stages dictionaries up to this many bytes in LDS
-constexpr uint32_t NL_IST = 12288;         // most dictionary-id bytes one k_flat_null block stages in LDS
-constexpr uint32_t NL_SLACK = 256;         // run-header bytes a block's level / id byte range may add
-// k_flat_null's dynamic LDS, per batch: level bytes (dcap), dictionary-id bytes (icap) a block may
-// stage -- from the batch's widest level / id bit width (host-known: max definition level, dictionary
-// size), FBLK values of it + NL_SLACK, at most NL_DST / NL_IST; k_lvl's block table is checked against
-// the same caps -- and the dictionary bytes it stages (dlds, 0: none). Multiples of 16.
-struct NullCaps {
-    uint32_t dcap, icap, dlds;
-};
-PF_HD inline uint32_t lvl_table_cap(int32_t num_values) {
-    // RLE runs are >= 8 repeats and bit-packed groups 8 values for the writers we know (parquet-mr,
-    // Arrow): <= 2 runs per 16 entries; a page needing more is left to k_flat / k_decode
-    return uint32_t(num_values) / 8u + 64u;
 }
 
 // One PLAIN BYTE_ARRAY length walk (a BYTE_ARRAY dictionary page, or the values section of a

@@ -140,13 +140,11 @@ __device__ inline uint32_t decode_level_tile(LevelLds& L, const Sections& s, con
 }
 
 // ---- values helpers ------------------------------------------------------------------------
-// BYTE_ARRAY data pages: chars of the entries before each block of FBLK entries (pf_internal.h: the
-// flat kernels split pages into blocks), written by the count kernels for dictionary pages and kept
-// after the page's aux entries.
+// BYTE_ARRAY data pages: chars of the entries before each block of FBLK entries (the flat kernels split
+// pages into blocks), written by the count kernels for dictionary pages (block_chars, pf_page_tables.h).
 __device__ __forceinline__ uint64_t* flat_block_chars(const DevPage& pg) {
     if (!pg.aux) return nullptr;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(pg.aux + pg.aux_cap + 1);
-    return reinterpret_cast<uint64_t*>((a + 7) & ~uintptr_t(7));
+    return block_chars(pg.aux, pg.aux_cap);
 }
 __device__ __forceinline__ bool is_dict_enc(int e) { return e == 2 || e == 8; }
 
@@ -407,13 +405,30 @@ __device__ __forceinline__ uint32_t bits_fast(const uint8_t* p, uint32_t sh, int
 }
 
 // Index of the run holding value i (runs sorted by `first`, runs[0].first == 0).
-__device__ __forceinline__ int run_find(const Run* runs, int nr, uint32_t i) {
-    int lo = 0, hi = nr;
+// Last of rows [0, nr) whose first(row) <= key (row 0 when none is): the run tables' binary search,
+// in the caller's index type I.
+template <class I, class F>
+__device__ __forceinline__ I last_row_le(I nr, uint32_t key, F first) {
+    I lo = 0, hi = nr;
     while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (runs[mid].first <= i) lo = mid; else hi = mid;
+        const I mid = (lo + hi) >> 1;
+        if (first(mid) <= key) lo = mid; else hi = mid;
     }
     return lo;
+}
+__device__ __forceinline__ int run_find(const Run* runs, int nr, uint32_t i) {
+    return last_row_le(nr, i, [runs](int r) { return runs[r].first; });
+}
+// Row i of a page's id run table (k_runs) as a Run; nr, cov: the table's nruns and covered
+__device__ __forceinline__ Run id_run(const IdRunTab* T, uint32_t i, uint32_t nr, uint32_t cov) {
+    const uint32_t f = T->fp(i);
+    const uint32_t nf = i + 1 < nr ? T->first(i + 1) : cov;
+    Run r;
+    r.first = f & 0x7fffffffu;
+    r.count = nf - r.first;
+    r.data = T->data(i);
+    r.packed = f >> 31;
+    return r;
 }
 
 __device__ __forceinline__ uint32_t run_value(const Run& r, const uint8_t* p, uint64_t n, uint32_t i, int bw) {

@@ -70,10 +70,6 @@ constexpr int FTX = PF_FTX;          // tile of the all-present fixed-width path
                                      // tiles' id loads and gathers per thread in flight together
 constexpr int FEPTX = FTX / NT;
 static_assert(FTX <= int(FBLK) && FBLK % FTX == 0, "fixed-width tiles divide blocks");
-#ifndef PF_RUN_CAP
-#define PF_RUN_CAP 256
-#endif
-constexpr int RUN_CAP = PF_RUN_CAP;
 constexpr uint32_t DSTR_CAP = 256;   // string dictionaries up to this many entries: {pos, len} staged in LDS
 
 // One 128-thread workgroup per dictionary data page of a flat chunk: walks the page's
@@ -87,13 +83,13 @@ __global__ __launch_bounds__(128) void k_runs(const DevChunk* __restrict__ chunk
     __shared__ uint32_t s_cov;
     const int pi = list[blockIdx.x];
     DevPage& pg = pages[pi];
-    uint32_t* T = pg.runtab;
+    IdRunTab* T = pg.runtab;
     if (!T) return;
     const DevChunk& ck = chunks[pg.chunk];
     const int tid = threadIdx.x;
     Sections s;
     if (res[pg.chunk].status != 0 || !page_sections(pg, ck, s) || s.val_n == 0 || s.val[0] > 32) {
-        if (tid == 0) T[3] = 0;
+        if (tid == 0) T->all_present = 0;
         return;
     }
     const uint32_t ne = uint32_t(pg.num_values);
@@ -110,25 +106,22 @@ __global__ __launch_bounds__(128) void k_runs(const DevChunk* __restrict__ chunk
     __syncthreads();
     const int nr = s_nr;
     if (s_res == 2) {   // too many runs for the table: blocks walk themselves
-        if (tid == 0) { T[2] = 0; T[3] = 0; }
+        if (tid == 0) { T->valid = 0; T->all_present = 0; }
         return;
     }
     for (int i = tid; i < nr; i += 128) {
-        T[4 + 2 * i] = R[i].first | (R[i].packed << 31);
-        T[5 + 2 * i] = R[i].data;
+        T->fp(i) = R[i].first | (R[i].packed << 31);
+        T->data(i) = R[i].data;
     }
-    // T[2]: the id table is valid (indexed by value: pages with nulls hold fewer ids than entries, the
-    // walk then ends with the stream); T[3]: valid and every level present (k_flat_fixed / k_flat split)
-    if (tid == 0) { T[0] = uint32_t(nr); T[1] = s_cov; T[2] = 1u; T[3] = s_allp ? 1u : 0u; }
+    if (tid == 0) { T->nruns = uint32_t(nr); T->covered = s_cov; T->valid = 1u; T->all_present = s_allp ? 1u : 0u; }
 }
 
-// Dictionary-string pages k_count_flat takes: flat, levels all present (k_runs: T[3]), a run table.
+// Dictionary-string pages k_count_flat takes: flat, levels all present (k_runs), a run table.
 __device__ __forceinline__ bool count_dict_page(const DevPage& pg, const DevChunk& ck, const Sections& s) {
-    const uint32_t* T = pg.runtab;
-    return T != nullptr && T[3] == 1u && T[0] <= uint32_t(RUN_CAP) && T[1] >= uint32_t(pg.num_values) && ck.dict_len &&
+    const IdRunTab* T = pg.runtab;
+    return T != nullptr && T->all_present == 1u && T->nruns <= uint32_t(RUN_CAP) && T->covered >= uint32_t(pg.num_values) && ck.dict_len &&
            s.val_n > 0 && flat_block_chars(pg) != nullptr;
 }
-constexpr uint64_t BC_BAD = ~0ull;   // a block's chars word when one of its ids is out of the dictionary
 
 // k_count_dict (round 5): the chars of one 4096-entry block of a flat dictionary BYTE_ARRAY page per
 // workgroup -- the block's ids from the page's run table (k_runs), their dictionary lengths summed --
@@ -151,18 +144,9 @@ __global__ __launch_bounds__(NT) void k_count_dict(const DevChunk* __restrict__ 
     const uint32_t b0 = uint32_t(pb.y) * FBLK;
     if (pb.y > 0 && b0 >= ne) return;
     const uint32_t b1 = min(ne, b0 + FBLK);
-    const uint32_t* T = pg.runtab;
-    const uint32_t nr = T[0], cov = T[1];
-    for (uint32_t i = tid; i < nr; i += NT) {
-        const uint32_t f = T[4 + 2 * i];
-        const uint32_t nf = i + 1 < nr ? (T[4 + 2 * (i + 1)] & 0x7fffffffu) : cov;
-        Run r;
-        r.first = f & 0x7fffffffu;
-        r.count = nf - r.first;
-        r.data = T[5 + 2 * i];
-        r.packed = f >> 31;
-        R[i] = r;
-    }
+    const IdRunTab* T = pg.runtab;
+    const uint32_t nr = T->nruns, cov = T->covered;
+    for (uint32_t i = tid; i < nr; i += NT) R[i] = id_run(T, i, nr, cov);
     const bool lstage = ck.dict_n > 0 && ck.dict_n <= int64_t(DSTR_CAP);
     if (lstage)
         for (uint32_t i = tid; i < uint32_t(ck.dict_n); i += NT) s_len[i] = gptr(ck.dict_len)[i];
@@ -803,9 +787,9 @@ __device__ __forceinline__ bool flat_fixed_block(FixedLds& S, const DevChunk* __
     const int id_bw = (dict && s.val_n > 0) ? int(s.val[0]) : 0;
     const uint8_t* ids = dict && s.val_n > 0 ? s.val + 1 : s.val;
     const uint64_t ids_n = dict && s.val_n > 0 ? s.val_n - 1 : 0;
-    const uint32_t* T = pg.runtab;
+    const IdRunTab* T = pg.runtab;
     uint32_t t0 = 0, t3 = 0;
-    if (T != nullptr) { t0 = T[0]; t3 = T[3]; }
+    if (T != nullptr) { t0 = T->nruns; t3 = T->all_present; }
     const bool tab = (t3 == 1u) & (t0 <= uint32_t(RUN_CAP));   // k_runs: levels all present
     if (tid == 0)
         S.allp = tab ? 1 : (ck.max_def == 0 ? 1 : all_present(s.def, s.def_n, bit_width(ck.max_def), ne, uint32_t(ck.max_def)));
@@ -818,17 +802,8 @@ __device__ __forceinline__ bool flat_fixed_block(FixedLds& S, const DevChunk* __
 #endif
     if (dict) {
         if (tab) {
-            const uint32_t nr = T[0], cov = T[1];
-            for (uint32_t i = tid; i < nr; i += NT) {
-                const uint32_t f = T[4 + 2 * i];
-                const uint32_t nf = i + 1 < nr ? (T[4 + 2 * (i + 1)] & 0x7fffffffu) : cov;
-                Run r;
-                r.first = f & 0x7fffffffu;
-                r.count = nf - r.first;
-                r.data = T[5 + 2 * i];
-                r.packed = f >> 31;
-                S.vrun[i] = r;
-            }
+            const uint32_t nr = T->nruns, cov = T->covered;
+            for (uint32_t i = tid; i < nr; i += NT) S.vrun[i] = id_run(T, i, nr, cov);
             if (tid == 0) { S.nvrun = int(nr); S.vcover = cov; S.vlo = 0; S.vres = cov >= ne ? 0 : 1; }
         } else if (tid < 64) {   // wave 0 walks the id runs of this block
             if (tid == 0) { S.nvrun = 0; S.vcover = 0; S.vres = 0; S.vlo = e_begin; S.vst = RunWalk{0, 0}; }
@@ -913,9 +888,9 @@ __device__ __forceinline__ void flat_block(FlatLds& S, const DevChunk* __restric
     const bool counted = ck.needs_count != 0;
     const uint64_t slot_base = uint64_t(pg.entry_start);   // flat: slot == entry
     if (blk > 0 && blk * bsz >= ne) return;
-    const uint32_t* T = pg.runtab;
+    const IdRunTab* T = pg.runtab;
     uint32_t t0 = 0, t3 = 0;
-    if (T != nullptr) { t0 = T[0]; t3 = T[3]; }
+    if (T != nullptr) { t0 = T->nruns; t3 = T->all_present; }
     const bool tab = (t3 == 1u) & (t0 <= uint32_t(RUN_CAP));   // k_runs: levels all present
     if (tid == 0) S.allp = tab ? 1 : (ck.max_def == 0 ? 1 : all_present(s.def, s.def_n, bwd, ne, uint32_t(ck.max_def)));
     __syncthreads();
@@ -942,17 +917,8 @@ __device__ __forceinline__ void flat_block(FlatLds& S, const DevChunk* __restric
         }
     }
     if (split && tab) {   // the page's run table (k_runs), loaded by all threads
-        const uint32_t nr = T[0], cov = T[1];
-        for (uint32_t i = tid; i < nr; i += NT) {
-            const uint32_t f = T[4 + 2 * i];
-            const uint32_t nf = i + 1 < nr ? (T[4 + 2 * (i + 1)] & 0x7fffffffu) : cov;
-            Run r;
-            r.first = f & 0x7fffffffu;
-            r.count = nf - r.first;
-            r.data = T[5 + 2 * i];
-            r.packed = f >> 31;
-            S.vrun[i] = r;
-        }
+        const uint32_t nr = T->nruns, cov = T->covered;
+        for (uint32_t i = tid; i < nr; i += NT) S.vrun[i] = id_run(T, i, nr, cov);
         if (tid == 0) { S.nvrun = int(nr); S.vcover = cov; S.vlo = 0; S.vres = cov >= ne ? 0 : 1; }
     }
     // small string dictionaries: {pos, len} from LDS (visible after the tile loop's first barrier)
@@ -1303,8 +1269,8 @@ __global__ __launch_bounds__(NT, PF_DSTR_OCC) void k_flat_dstr(const DevChunk* _
         return;
     }
     const uint32_t b1 = min(ne, b0 + FBLK);
-    const uint32_t* T = pg.runtab;
-    const uint32_t nr = T[0], cov = T[1];
+    const IdRunTab* T = pg.runtab;
+    const uint32_t nr = T->nruns, cov = T->covered;
     const uint32_t dn = uint32_t(ck.dict_n), dbytes = uint32_t(dend - dbeg);
     const int id_bw = int(s.val[0]);
     const uint8_t* ids = s.val + 1;
@@ -1314,8 +1280,8 @@ __global__ __launch_bounds__(NT, PF_DSTR_OCC) void k_flat_dstr(const DevChunk* _
     int bad = 0;
     uint32_t mylo = 0xffffffffu, myhi = 0u;   // id bytes [mylo, myhi) of this thread's run inside the block
     if (uint32_t(tid) < nr) {
-        const uint32_t f = T[4 + 2 * tid], d = T[5 + 2 * tid];
-        const uint32_t nf = uint32_t(tid) + 1 < nr ? (T[6 + 2 * tid] & 0x7fffffffu) : cov;
+        const uint32_t f = T->fp(tid), d = T->data(tid);
+        const uint32_t nf = uint32_t(tid) + 1 < nr ? T->next_first(tid) : cov;
         S.rt[2 * tid] = f;
         S.rt[2 * tid + 1] = d;
         const uint32_t first = f & 0x7fffffffu;
@@ -1511,23 +1477,18 @@ __device__ __forceinline__ uint32_t lds_bits(const uint8_t* st, uint32_t bit, ui
     return uint32_t(v >> sh) & (k >= 32 ? 0xffffffffu : ((1u << k) - 1u));
 }
 
-// Last level run with first entry <= e (runs: k_lvl table rows of 4 words, runs[0].first == 0).
-__device__ __forceinline__ uint32_t lvl_run_at(const uint32_t* runs, uint32_t nr, uint32_t e) {
-    uint32_t lo = 0, hi = nr;
-    while (hi - lo > 1) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (runs[4 * m] <= e) lo = m; else hi = m;
-    }
-    return lo;
+// Last level run with first entry <= e (runs: k_lvl's run rows, runs[0].first == 0).
+__device__ __forceinline__ uint32_t lvl_run_at(const LvlRun* runs, uint32_t nr, uint32_t e) {
+    return last_row_le(nr, e, [runs](uint32_t r) { return lvl_run(runs, r).first; });
 }
 // Present values before entry e, which lies in run r (its present-before count plus the present
 // levels of the run before e, from the staged level section).
-__device__ inline uint32_t lvl_values_before(const uint32_t* runs, uint32_t r, uint32_t e, const uint8_t* stage,
+__device__ inline uint32_t lvl_values_before(const LvlRun* runs, uint32_t r, uint32_t e, const uint8_t* stage,
                                              uint32_t woff, int bw, uint32_t maxd) {
-    const uint32_t first = runs[4 * r], data = runs[4 * r + 1], cw = runs[4 * r + 2];
+    const uint32_t first = lvl_run(runs, r).first, data = lvl_run(runs, r).data;
     const uint32_t before = e - first;
-    uint32_t vb = runs[4 * r + 3];
-    if (!(cw >> 31)) return vb + (data == maxd ? before : 0u);
+    uint32_t vb = lvl_run(runs, r).before;
+    if (!lvl_run(runs, r).packed()) return vb + (data == maxd ? before : 0u);
     if (bw == 1) {
         for (uint32_t i = 0; i < before; i += 32) {
             const uint32_t k = min(32u, before - i), bb = woff * 8u + data + i;
@@ -1541,15 +1502,9 @@ __device__ inline uint32_t lvl_values_before(const uint32_t* runs, uint32_t r, u
     }
     return vb;
 }
-// Dictionary-id run (k_runs table T: {nruns, covered, valid, -}, then {first | packed << 31, data})
-// holding value v.
-__device__ __forceinline__ uint32_t id_run_at(const uint32_t* T, uint32_t nr, uint32_t v) {
-    uint32_t lo = 0, hi = nr;
-    while (hi - lo > 1) {
-        const uint32_t m = (lo + hi) >> 1;
-        if ((T[4 + 2 * m] & 0x7fffffffu) <= v) lo = m; else hi = m;
-    }
-    return lo;
+// Dictionary-id run (k_runs table T) holding value v.
+__device__ __forceinline__ uint32_t id_run_at(const IdRunTab* T, uint32_t nr, uint32_t v) {
+    return last_row_le(nr, v, [T](uint32_t r) { return T->first(r); });
 }
 
 constexpr int LT_NT = 256;                // k_lvl: four waves per page
@@ -1571,30 +1526,30 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
     // next-header positions of every byte position (0xffff: not a header, or its run passes the
     // section end; dn: the chain ends there), then the page's dictionary-id runs (k_runs) for the
     // block table
-    __shared__ union { uint16_t nxt[LVL_NXT]; uint32_t T[4 + 2 * RUN_CAP]; } s_u;
+    __shared__ union { uint16_t nxt[LVL_NXT]; IdRunTab T; } s_u;
     // the 8-run jump table during the chain walk, then the LDS copy of the level runs
-    __shared__ union { uint16_t jmp[LVL_NXT]; uint32_t runs[4 * LVL_RUNS_LDS]; } s_a;
+    __shared__ union { uint16_t jmp[LVL_NXT]; LvlRun runs[LVL_RUNS_LDS]; } s_a;
     __shared__ uint16_t s_s8[LVL_S8];         // chain positions of runs 0, 8, 16, ...
     __shared__ uint32_t s_mark[LVL_NXT / 32];  // chain positions (run headers)
-    static_assert(sizeof(uint16_t) * LVL_NXT >= sizeof(uint32_t) * (4 + 2 * RUN_CAP), "s_u sized by the header table");
+    static_assert(sizeof(uint16_t) * LVL_NXT >= sizeof(IdRunTab), "s_u sized by the header table");
     uint16_t* const s_nxt = s_u.nxt;
-    uint32_t* const s_T = s_u.T;
+    IdRunTab* const s_T = &s_u.T;
     uint16_t* const s_jmp = s_a.jmp;
-    uint32_t* const s_runs = s_a.runs;
+    LvlRun* const s_runs = s_a.runs;
     const int pi = list[blockIdx.x];
     DevPage& pg = pages[pi];
-    uint32_t* LT = pg.lvltab;
+    LvlHead* LT = pg.lvltab;
     if (!LT) return;
     const DevChunk& ck = chunks[pg.chunk];
     const int tid = threadIdx.x;
     Sections s;
     if (pg.done & DONE_PAGE) {   // k_page_null decoded the page
-        if (tid == 0) LT[1] = 0;
+        if (tid == 0) LT->fit = 0;
         return;
     }
     if (res[pg.chunk].status != 0 || ck.max_rep != 0 || ck.max_def <= 0 || !page_sections(pg, ck, s) || !s.def_rle ||
         s.def_n > LVL_STAGE) {   // (longer level sections: k_flat / k_decode)
-        if (tid == 0) LT[1] = 0;
+        if (tid == 0) LT->fit = 0;
         return;
     }
     const uint32_t ne = uint32_t(pg.num_values);
@@ -1614,7 +1569,7 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
     const uintptr_t sa = reinterpret_cast<uintptr_t>(s.def);
     const uint32_t woff = uint32_t(sa & 15u);
     if (woff + dn > LVL_STAGE) {
-        if (tid == 0) LT[1] = 0;
+        if (tid == 0) LT->fit = 0;
         return;
     }
     {
@@ -1627,7 +1582,7 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
         __syncthreads();
     }
     LTS(9);
-    uint32_t* runs = LT + 4;
+    LvlRun* runs = lvl_runs(LT);
     const uint32_t cap = pg.lvl_cap;
     const uint8_t* const stw = stage + woff;
     // (1) every byte position decoded as a run header: the position of the next header
@@ -1746,13 +1701,13 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
             if ((emask >> k) & 1u && nr <= cap) {   // (emitted: f < ne)
                 const uint32_t c = uint32_t(min<uint64_t>(hcnt[k], uint64_t(ne) - f));
                 const uint32_t cw = c | (((hpk >> k) & 1u) << 31);
-                runs[4 * rank + 0] = uint32_t(f);
-                runs[4 * rank + 1] = hdat[k];
-                runs[4 * rank + 2] = cw;
+                lvl_run(runs, rank).first = uint32_t(f);
+                lvl_run(runs, rank).data = hdat[k];
+                lvl_run(runs, rank).cw = cw;
                 if (rank < LVL_RUNS_LDS) {
-                    s_runs[4 * rank + 0] = uint32_t(f);
-                    s_runs[4 * rank + 1] = hdat[k];
-                    s_runs[4 * rank + 2] = cw;
+                    lvl_run(s_runs, rank).first = uint32_t(f);
+                    lvl_run(s_runs, rank).data = hdat[k];
+                    lvl_run(s_runs, rank).cw = cw;
                 }
                 rank++;
             }
@@ -1763,18 +1718,17 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
     const bool ok = __syncthreads_or(bad) == 0 && nr <= cap && ctot >= ne;   // (a broken chain covers too few)
     LTS(12);
     if (!ok) {
-        if (tid == 0) LT[1] = 0;
+        if (tid == 0) LT->fit = 0;
         return;
     }
-    uint32_t* const R = nr <= LVL_RUNS_LDS ? s_runs : runs;   // the scans below read this copy
+    LvlRun* const R = nr <= LVL_RUNS_LDS ? s_runs : runs;   // the scans below read this copy
     uint32_t carry = 0;
     for (uint32_t r0 = 0; r0 < nr; r0 += LT_NT) {
         const uint32_t r = r0 + uint32_t(tid);
         uint32_t pc = 0;
         if (r < nr) {
-            const uint32_t data = R[4 * r + 1], cw = R[4 * r + 2];
-            const uint32_t cnt = cw & 0x7fffffffu;
-            if (!(cw >> 31)) pc = data == maxd ? cnt : 0u;
+            const uint32_t data = lvl_run(R, r).data, cnt = lvl_run(R, r).count();
+            if (!lvl_run(R, r).packed()) pc = data == maxd ? cnt : 0u;
             else {
                 // packed levels [data, data + cnt * bw) bits (the stage is zero past the section)
                 const uint32_t nbits = cnt * uint32_t(bw);
@@ -1795,8 +1749,8 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
         uint32_t tot;
         const uint32_t ex = block_excl_scan<LT_NT>(pc, scan_tmp, tot);
         if (r < nr) {
-            runs[4 * r + 3] = carry + ex;
-            if (R != runs) R[4 * r + 3] = carry + ex;
+            lvl_run(runs, r).before = carry + ex;
+            if (R != runs) lvl_run(R, r).before = carry + ex;
         }
         carry += tot;
         __syncthreads();   // scan_tmp is reused
@@ -1805,16 +1759,16 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
     // per FBLK block (k_flat_null): the runs it overlaps [r0, r1), the value indices of its first and
     // end entries, the level bytes its packed runs read and the dictionary-id bytes of its values
     __threadfence_block();
-    uint32_t* BT = runs + 4 * cap;
     const uint32_t nblk = (ne + FBLK - 1) / FBLK;
     // dictionary id runs (k_runs, same stream): value index -> bit offset in the id stream
-    const uint32_t* TG = pg.runtab;
-    const bool dict = is_dict_enc(pg.encoding) && TG != nullptr && TG[2] == 1u && TG[0] <= uint32_t(RUN_CAP) && s.val_n > 0;
-    const uint32_t tnr = dict ? TG[0] : 0u, tcov = dict ? TG[1] : 0u;
+    const IdRunTab* TG = pg.runtab;
+    const bool dict = is_dict_enc(pg.encoding) && TG != nullptr && TG->valid == 1u && TG->nruns <= uint32_t(RUN_CAP) && s.val_n > 0;
+    const uint32_t tnr = dict ? TG->nruns : 0u, tcov = dict ? TG->covered : 0u;
     if (dict)
-        for (uint32_t i = tid; i < 4 + 2 * tnr; i += LT_NT) s_T[i] = TG[i];
+        for (uint32_t i = tid; i < id_tab_words(tnr); i += LT_NT)
+            reinterpret_cast<uint32_t*>(s_T)[i] = reinterpret_cast<const uint32_t*>(TG)[i];
     __syncthreads();
-    const uint32_t* T = s_T;
+    const IdRunTab* T = s_T;
     const uint32_t id_bw = dict ? uint32_t(s.val[0]) : 0u;
     uint32_t fit = 1;
     for (uint32_t b = tid; b < nblk; b += LT_NT) {
@@ -1823,24 +1777,22 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
         uint32_t a = lo, z = nr;    // first run with first >= ee
         while (a < z) {
             const uint32_t m = (a + z) >> 1;
-            if (R[4 * m] < ee) a = m + 1; else z = m;
+            if (lvl_run(R, m).first < ee) a = m + 1; else z = m;
         }
         const uint32_t vb = lvl_values_before(R, lo, eb, stage, woff, bw, maxd);
         const uint32_t ve = ee == ne ? carry : lvl_values_before(R, lvl_run_at(R, nr, ee), ee, stage, woff, bw, maxd);
         // level bytes: from the first packed run's first bit to the last packed run's end
         uint32_t d0 = 0, d1 = 0;
         for (uint32_t r = lo; r < a; r++) {
-            const uint32_t cw = R[4 * r + 2];
-            if (!(cw >> 31)) continue;
-            const uint32_t f = R[4 * r];
-            d0 = (R[4 * r + 1] + (max(eb, f) - f) * uint32_t(bw)) >> 3;
+            if (!lvl_run(R, r).packed()) continue;
+            const uint32_t f = lvl_run(R, r).first;
+            d0 = (lvl_run(R, r).data + (max(eb, f) - f) * uint32_t(bw)) >> 3;
             break;
         }
         for (uint32_t r = a; r > lo; r--) {
-            const uint32_t cw = R[4 * (r - 1) + 2];
-            if (!(cw >> 31)) continue;
-            const uint32_t f = R[4 * (r - 1)], end = min(ee, f + (cw & 0x7fffffffu));
-            d1 = (R[4 * (r - 1) + 1] + (end - f) * uint32_t(bw) + 7u) >> 3;
+            if (!lvl_run(R, r - 1).packed()) continue;
+            const uint32_t f = lvl_run(R, r - 1).first, end = min(ee, f + lvl_run(R, r - 1).count());
+            d1 = (lvl_run(R, r - 1).data + (end - f) * uint32_t(bw) + 7u) >> 3;
             break;
         }
         // dictionary-id bytes of values [vb, ve)
@@ -1850,27 +1802,25 @@ __global__ __launch_bounds__(LT_NT, PF_LVL_OCC) void k_lvl(const DevChunk* __res
             else {
                 const uint32_t q0 = id_run_at(T, tnr, vb), q1 = id_run_at(T, tnr, ve - 1);
                 for (uint32_t q = q0; q <= q1; q++) {
-                    if (!(T[4 + 2 * q] >> 31)) continue;
-                    const uint32_t f = T[4 + 2 * q] & 0x7fffffffu;
-                    i0 = uint32_t((uint64_t(T[5 + 2 * q]) + uint64_t(max(vb, f) - f) * id_bw) >> 3);
+                    if (!T->packed(q)) continue;
+                    const uint32_t f = T->first(q);
+                    i0 = uint32_t((uint64_t(T->data(q)) + uint64_t(max(vb, f) - f) * id_bw) >> 3);
                     break;
                 }
                 for (uint32_t q = q1 + 1; q > q0; q--) {
-                    if (!(T[4 + 2 * (q - 1)] >> 31)) continue;
-                    const uint32_t f = T[4 + 2 * (q - 1)] & 0x7fffffffu;
-                    const uint32_t nf = q < tnr ? (T[4 + 2 * q] & 0x7fffffffu) : tcov;
-                    i1 = uint32_t((uint64_t(T[5 + 2 * (q - 1)]) + uint64_t(min(ve, nf) - f) * id_bw + 7u) >> 3);
+                    if (!T->packed(q - 1)) continue;
+                    const uint32_t f = T->first(q - 1);
+                    const uint32_t nf = q < tnr ? T->first(q) : tcov;
+                    i1 = uint32_t((uint64_t(T->data(q - 1)) + uint64_t(min(ve, nf) - f) * id_bw + 7u) >> 3);
                     break;
                 }
             }
         }
         if (a - lo > LT_BLOCK_RUNS || d1 - d0 + 16u > dcap || i1 - i0 + 16u > icap || ve < vb) fit = 0;
-        uint32_t* bt = BT + LT_BT_WORDS * b;
-        bt[0] = lo; bt[1] = a; bt[2] = vb; bt[3] = ve;
-        bt[4] = d0; bt[5] = d1; bt[6] = i0; bt[7] = i1;
+        *lvl_block(LT, cap, b) = LvlBlock{lo, a, vb, ve, d0, d1, i0, i1};
     }
     fit = __syncthreads_and(fit) ? 1u : 0u;
-    if (tid == 0) { LT[0] = nr; LT[2] = carry; LT[1] = fit; }
+    if (tid == 0) { LT->nruns = nr; LT->present = carry; LT->fit = fit; }
     LTS(14);
 #ifdef PF_STAMPS
     if (tid == 0) PSTAMP(15, __builtin_amdgcn_s_memtime() - lt0_);
@@ -1903,12 +1853,7 @@ struct NullLds {
 };
 __device__ __forceinline__ uint32_t rl_first(uint2 r) { return r.x & 0x7fffffffu; }
 __device__ __forceinline__ int rl_find(const uint2* runs, int nr, uint32_t i) {   // run holding i (runs[0] first <= i)
-    int lo = 0, hi = nr;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rl_first(runs[mid]) <= i) lo = mid; else hi = mid;
-    }
-    return lo;
+    return last_row_le(nr, i, [runs](int r) { return rl_first(runs[r]); });
 }
 
 // Dynamic LDS, sized by the host per batch (NullCaps): the block's level bytes (dcap + 32), its
@@ -1951,20 +1896,20 @@ __global__ __launch_bounds__(NTN) void k_flat_null(const DevChunk* __restrict__ 
     DevPage& pg = pages[pi];
     const DevChunk& ck = chunks[pg.chunk];
     const int tid = threadIdx.x;
-    const uint32_t* LT = pg.lvltab;
+    LvlHead* const LT = pg.lvltab;
     // pages this kernel does not take (whole pages: the conditions are the page's) go to the fallback queue
     // (not DONE_NULL: blocks of this page that finished first set it, and a block starting later must still run)
     if (!LT || res[pg.chunk].status != 0 || ck.max_rep != 0 || ck.width != W ||
-        (pg.done & (DONE_FIXED | DONE_PAGE)) || LT[1] != 1u) {   // (k_page_null took it, or no block table)
+        (pg.done & (DONE_FIXED | DONE_PAGE)) || LT->fit != 1u) {   // (k_page_null took it, or no block table)
         null_fallback(fbq, pbk);
         return;
     }
     Sections s;
     const int enc = pg.encoding;
     const bool dict = is_dict_enc(enc);
-    const uint32_t* T = pg.runtab;
+    const IdRunTab* T = pg.runtab;
     if (!page_sections(pg, ck, s) || (!dict && enc != 0) ||
-        (dict && !(T != nullptr && T[2] == 1u && T[0] <= uint32_t(RUN_CAP) && s.val_n > 0 && ck.dict_data != nullptr))) {
+        (dict && !(T != nullptr && T->valid == 1u && T->nruns <= uint32_t(RUN_CAP) && s.val_n > 0 && ck.dict_data != nullptr))) {
         null_fallback(fbq, pbk);
         return;
     }
@@ -1975,13 +1920,13 @@ __global__ __launch_bounds__(NTN) void k_flat_null(const DevChunk* __restrict__ 
     constexpr int w = W;
     const int bw = bit_width(uint32_t(ck.max_def));
     const uint32_t maxd = uint32_t(ck.max_def);
-    const uint32_t nr = LT[0];
-    const uint32_t* runs = LT + 4;
-    const uint32_t* bt = runs + 4 * pg.lvl_cap + LT_BT_WORDS * blk;
-    const uint32_t r0 = bt[0], r1 = bt[1], vb = bt[2], ve = bt[3], d0 = bt[4], d1 = bt[5], i0 = bt[6], i1 = bt[7];
+    const uint32_t nr = LT->nruns;
+    const LvlRun* runs = lvl_runs(LT);
+    const LvlBlock& bt = *lvl_block(LT, pg.lvl_cap, blk);
+    const uint32_t r0 = bt.r0, r1 = bt.r1, vb = bt.vb, ve = bt.ve, d0 = bt.d0, d1 = bt.d1, i0 = bt.i0, i1 = bt.i1;
     const uint32_t id_bw = dict ? uint32_t(s.val[0]) : 0u;
-    const uint32_t vnr = dict ? T[0] : 0u;
-    const uint32_t idcov = dict ? T[1] : 0u;
+    const uint32_t vnr = dict ? T->nruns : 0u;
+    const uint32_t idcov = dict ? T->covered : 0u;
     const uint8_t* ids = dict ? s.val + 1 : nullptr;
     const uint64_t ids_n = dict ? s.val_n - 1 : 0;
     if (r1 < r0 || (r1 == r0 && e_end > e_begin) || r1 - r0 > LT_BLOCK_RUNS || r1 > nr || id_bw > 32 || ve < vb || d1 < d0 || d1 - d0 + 16u > nc.dcap ||
@@ -1993,13 +1938,13 @@ __global__ __launch_bounds__(NTN) void k_flat_null(const DevChunk* __restrict__ 
     // one round of loads: level runs, id runs, level bytes, id bytes
     const uint32_t nrun = r1 - r0;
     for (uint32_t i = tid; i < nrun; i += NTN) {
-        const uint32_t* q = runs + 4 * (r0 + i);
-        const uint32_t f = q[0], d = q[1], c = q[2];
+        const LvlRun& q = lvl_run(runs, r0 + i);
+        const uint32_t f = q.first, d = q.data, c = q.cw;
         S.drun[i] = make_uint2(f | (c & 0x80000000u), d);
         if (i + 1 == nrun) S.drun[nrun] = make_uint2(f + (c & 0x7fffffffu), 0u);
     }
     for (uint32_t i = tid; i <= vnr; i += NTN)
-        S.vrun[i] = i < vnr ? make_uint2(T[4 + 2 * i], T[5 + 2 * i]) : make_uint2(idcov, 0u);
+        S.vrun[i] = i < vnr ? make_uint2(T->fp(i), T->data(i)) : make_uint2(idcov, 0u);
     const uint32_t doff = stage_bytes(s_dst, s.def, s.def_n, d0, d1);
     const uint32_t ioff = dict ? stage_bytes(s_ist, ids, ids_n, i0, i1) : 0u;
     for (uint32_t i = tid; i < FBLK / 32 + 2; i += NTN) S.vbits[i] = 0;
@@ -2218,7 +2163,7 @@ __global__ __launch_bounds__(PN_NT) void k_page_null(const DevChunk* __restrict_
     DevPage& pg = pages[pi];
     const DevChunk& ck = chunks[pg.chunk];
     const int tid = threadIdx.x;
-    const uint32_t* T = pg.runtab;
+    const IdRunTab* T = pg.runtab;
     Sections s;
     const int w = ck.width;
     const bool dict = is_dict_enc(pg.encoding);
@@ -2230,9 +2175,9 @@ __global__ __launch_bounds__(PN_NT) void k_page_null(const DevChunk* __restrict_
                 s.def_rle && s.def_n > 0 && s.def_n <= LVL_STAGE;
     uint32_t id_bw = 0, idn = 0, vnr = 0, idcov = 0;
     if (take && dict) {
-        take = T != nullptr && T[2] == 1u && T[0] <= uint32_t(RUN_CAP) && T[0] > 0 && s.val_n > 1 && s.val[0] <= 32 &&
+        take = T != nullptr && T->valid == 1u && T->nruns <= uint32_t(RUN_CAP) && T->nruns > 0 && s.val_n > 1 && s.val[0] <= 32 &&
                s.val_n - 1 <= PN_IST && ck.dict_data != nullptr && ck.dict_n > 0;
-        if (take) { id_bw = s.val[0]; idn = uint32_t(s.val_n - 1); vnr = T[0]; idcov = T[1]; }
+        if (take) { id_bw = s.val[0]; idn = uint32_t(s.val_n - 1); vnr = T->nruns; idcov = T->covered; }
     }
     if (!take) return;
     const int bw = bit_width(uint32_t(ck.max_def));
@@ -2241,16 +2186,7 @@ __global__ __launch_bounds__(PN_NT) void k_page_null(const DevChunk* __restrict_
     // ---- stage: level bytes, id bytes, id runs (one round of loads)
     const uint32_t doff = stage_bytes(S.lv, s.def, dn, 0, dn);
     const uint32_t ioff = dict ? stage_bytes(S.ist, s.val + 1, idn, 0, idn) : 0u;
-    for (uint32_t i = tid; i < vnr; i += PN_NT) {
-        const uint32_t f = T[4 + 2 * i];
-        const uint32_t nf = i + 1 < vnr ? (T[4 + 2 * (i + 1)] & 0x7fffffffu) : idcov;
-        Run r;
-        r.first = f & 0x7fffffffu;
-        r.count = nf - r.first;
-        r.data = T[5 + 2 * i];
-        r.packed = f >> 31;
-        S.vrun[i] = r;
-    }
+    for (uint32_t i = tid; i < vnr; i += PN_NT) S.vrun[i] = id_run(T, i, vnr, idcov);
     __syncthreads();
     const uint8_t* lv8 = reinterpret_cast<const uint8_t*>(S.lv);
     const uint8_t* stw = lv8 + doff;   // stw[i] = level section byte i (zero past the section)

@@ -175,7 +175,7 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                 // FIXED_LEN_BYTE_ARRAY in DELTA_BYTE_ARRAY (parquet-mr's v2 writer after a dictionary fallback)
                 const bool flba_dba = cd.physical_type == PF_FIXED_LEN_BYTE_ARRAY && pd.encoding == PF_ENC_DELTA_BYTE_ARRAY;
                 if (cd.physical_type == PF_BYTE_ARRAY)   // value positions / ids + per-block chars (k_flat)
-                    pp.aux_off = take(scratch, 4ull * pd.num_values + 16 + 8ull * (uint64_t(pd.num_values) / FBLK + 2), 256);
+                    pp.aux_off = take(scratch, aux_chars_bytes(uint64_t(pd.num_values)), 256);
                 else if (flba_dba)   // slot of every present value (decode_page -> k_dba_chars)
                     pp.aux_off = take(scratch, 4ull * pd.num_values + 16, 256);
                 else if (pd.encoding == PF_ENC_DELTA_BINARY_PACKED && int_type(cd.physical_type)) {
@@ -183,7 +183,7 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                     // block-parallel decode (k_dbp_*); PF_DBP_PAR=0: every page on the one-workgroup k_delta (tests)
                     if (pd.num_values >= DBP_PAR_MIN && opts.dbp_par) {
                         pg.dbp_bcap = uint32_t(pd.num_values / 8 + 2);
-                        pp.dbp_off = take(scratch, 12ull * pg.dbp_bcap + 16, 256);
+                        pp.dbp_off = take(scratch, dbp_bytes(pg.dbp_bcap), 256);
                         pg.dbp_nwin = int32_t((uint64_t(std::max(pd.uncompressed_size, pd.compressed_size)) + DBP_WIN - 1) / DBP_WIN + 1);
                         pp.dbp_pub_off = nest_pub;
                         nest_pub += uint64_t(pg.dbp_nwin) * sizeof(WinPub);
@@ -193,14 +193,13 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                 if (cd.physical_type == PF_BYTE_ARRAY) p.chars_hint += pd.uncompressed_size;
                 if (flba_dba || (cd.physical_type == PF_BYTE_ARRAY &&
                                  (pd.encoding == PF_ENC_DELTA_LENGTH_BYTE_ARRAY || pd.encoding == PF_ENC_DELTA_BYTE_ARRAY)))
-                    pp.dx_off = take(scratch, 8ull * (3ull * uint64_t(pd.num_values) + 1), 256);   // k_dlen
+                    pp.dx_off = take(scratch, dx_bytes(uint64_t(pd.num_values)), 256);   // k_dlen
                 if (cd.max_rep == 0 && cd.physical_type != PF_BOOLEAN && dict_encoded(pd.encoding))
                     pp.rt_off = take(scratch, RT_BYTES, 256);   // k_runs table
                 if (cd.max_rep == 0 && cd.max_def > 0 && cd.physical_type != PF_BOOLEAN && cd.physical_type != PF_BYTE_ARRAY &&
                     pd.num_nulls != 0 &&   // v2 header / v1 page statistics say when no level is null (-1: unknown)
                     (pd.encoding == PF_ENC_PLAIN || dict_encoded(pd.encoding))) {
-                    pp.lt_off = take(scratch, 16 + 16ull * lvl_table_cap(pd.num_values) +
-                                                  4ull * LT_BT_WORDS * (uint64_t(pd.num_values) / FBLK + 1), 256);   // k_lvl tables
+                    pp.lt_off = take(scratch, lvl_table_bytes(pg.num_values), 256);   // k_lvl tables
                     pg.lvl_cap = lvl_table_cap(pg.num_values);
                 }
                 {   // nested pages decoded in segments (k_nest_*): PLAIN fixed width, dictionary, DELTA_BINARY_PACKED ints
@@ -498,8 +497,8 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
         if (pg.flags & PG_V2) pg.lvl = src;
         pg.body = (pg.flags & PG_COMPRESSED) ? at(S, pp.scratch_off) : src + pg.rep_len + pg.def_len;
         pg.aux = words(at(S, pp.aux_off));
-        pg.runtab = words(at(S, pp.rt_off));
-        pg.lvltab = words(at(S, pp.lt_off));
+        pg.runtab = reinterpret_cast<IdRunTab*>(at(S, pp.rt_off));
+        pg.lvltab = reinterpret_cast<LvlHead*>(at(S, pp.lt_off));
         pg.dx = reinterpret_cast<uint64_t*>(at(S, pp.dx_off));
         pg.dbp = at(S, pp.dbp_off);
         pg.seg = at(S, pp.seg_off);

@@ -1169,7 +1169,7 @@ extern "C" int pf_debug_page_done(pf_ctx* ctx, int* out, int n_pages) {
         for (int i = 0; i < m; i++) {
             out[2 * i] = pg[size_t(i)].done;
             uint32_t lt1 = 0;   // k_lvl's "block table fits" word (k_flat_null ran on the page)
-            if (pg[size_t(i)].lvltab) HIPCHK(ctx, hipMemcpy(&lt1, pg[size_t(i)].lvltab + 1, 4, hipMemcpyDeviceToHost));
+            if (pg[size_t(i)].lvltab) HIPCHK(ctx, hipMemcpy(&lt1, &pg[size_t(i)].lvltab->fit, 4, hipMemcpyDeviceToHost));
             out[2 * i + 1] = int(lt1);
         }
     }

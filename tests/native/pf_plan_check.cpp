@@ -463,21 +463,23 @@ void hand_made() {
             for (size_t k = 0; k + 1 < p.lists[L_FLAT].size(); k += 2)
                 if (p.lists[L_FLAT][k] == 0) check((uint32_t(p.lists[L_FLAT][k + 1]) >> 28) == uint32_t(sh), "shift bits");
         }
-    // 2. nullable dictionary pages: level table and null grid only when the page may hold nulls
+    // 2. nullable dictionary pages: level table and null grid only when the page may hold nulls; the id run table
+    // always (4095, 4096, 4097 entries: the edges of the tables' per-block parts)
     for (int pt : {PF_INT32, PF_INT64})
-        for (int nulls : {-1, 0, 7}) {
-            Chunk c = chunk(pt, 1, 0, PF_CODEC_UNCOMPRESSED);
-            c.pages.push_back(page(PF_PAGE_DICTIONARY, PF_ENC_PLAIN, 100, 800, 800));
-            c.pages.push_back(page(PF_PAGE_DATA_V2, PF_ENC_RLE_DICTIONARY, 5000, 5000, 5000, nulls));
-            c.pages[1].def_bytes = 700;
-            std::snprintf(name, sizeof name, "2 nullable type %d nulls %d", pt, nulls);
-            run(name, {c}, PfOpts{}, p);
-            const bool tab = nulls != 0;
-            check((p.pages[1].lvltab != nullptr) == tab && p.lists[L_LVL].size() == size_t(tab), "level table");
-            check((pt == PF_INT32 ? p.n_null4 : p.n_null8) == (tab ? 8 : 0) && (pt == PF_INT32 ? p.n_null8 : p.n_null4) == 0 && p.n_flat_fixed == (tab ? 0 : 8), "null grid");
-            check(blocks_of(p, 1) == (tab ? 2 : 1), "blocks");
-            check((p.null_caps.dlds > 0) == tab && p.null_caps.dcap >= 16 && p.null_caps.dcap % 16 == 0 && p.null_caps.icap % 16 == 0 && p.null_caps.dcap <= NL_DST && p.null_caps.icap <= NL_IST, "null caps");
-        }
+        for (int nulls : {-1, 0, 7})
+            for (int nv : {5000, 4095, 4096, 4097}) {
+                Chunk c = chunk(pt, 1, 0, PF_CODEC_UNCOMPRESSED);
+                c.pages.push_back(page(PF_PAGE_DICTIONARY, PF_ENC_PLAIN, 100, 800, 800));
+                c.pages.push_back(page(PF_PAGE_DATA_V2, PF_ENC_RLE_DICTIONARY, nv, 5000, 5000, nulls));
+                c.pages[1].def_bytes = 700;
+                std::snprintf(name, sizeof name, "2 nullable type %d nulls %d, %d values", pt, nulls, nv);
+                run(name, {c}, PfOpts{}, p);
+                const bool tab = nulls != 0;
+                check((p.pages[1].lvltab != nullptr) == tab && p.lists[L_LVL].size() == size_t(tab) && p.pages[1].runtab != nullptr, "level table");
+                check((pt == PF_INT32 ? p.n_null4 : p.n_null8) == (tab ? 8 : 0) && (pt == PF_INT32 ? p.n_null8 : p.n_null4) == 0 && p.n_flat_fixed == (tab ? 0 : 8), "null grid");
+                check(blocks_of(p, 1) == (tab ? (nv + 4095) / 4096 : 1), "blocks");
+                check((p.null_caps.dlds > 0) == tab && p.null_caps.dcap >= 16 && p.null_caps.dcap % 16 == 0 && p.null_caps.icap % 16 == 0 && p.null_caps.dcap <= NL_DST && p.null_caps.icap <= NL_IST, "null caps");
+            }
     // 3. nested pages: segments
     struct N { int nv; bool set; int64_t seg; int nseg, seg_len; };
     for (const N& t : {N{2048, false, 0, 0, 0}, N{2049, false, 0, 2, 2048}, N{4095, false, 0, 2, 2048}, N{4096, false, 0, 2, 2048},
@@ -493,7 +495,7 @@ void hand_made() {
         check(p.n_decode_first == 1 && blocks_of(p, 0) == 0, "nested page routing");
     }
     // 4. DELTA_BINARY_PACKED: block-parallel from 16384 entries
-    for (int nv : {16383, 16384})
+    for (int nv : {16383, 16384, 16385})
         for (bool par : {true, false}) {
             PfOpts o; o.dbp_par = par;
             Chunk c = chunk(PF_INT64, 0, 0, PF_CODEC_UNCOMPRESSED);
@@ -505,18 +507,20 @@ void hand_made() {
         }
     // 4b. DELTA_BYTE_ARRAY: BYTE_ARRAY and FIXED_LEN_BYTE_ARRAY pages get k_dlen's tables (FLBA also a slot map) and
     // k_dba_chars; no other type does (k_decode reports the page)
+    // (4095, 4096, 4097 entries: the edges of the block chars behind a BYTE_ARRAY page's aux words)
     for (int pt : {PF_BYTE_ARRAY, PF_FIXED_LEN_BYTE_ARRAY, PF_INT32})
-        for (int rep : {0, 1}) {
-            Chunk c = chunk(pt, 1 + rep, rep, PF_CODEC_UNCOMPRESSED);
-            c.d.type_length = pt == PF_FIXED_LEN_BYTE_ARRAY ? 7 : 0;
-            c.pages.push_back(page(PF_PAGE_DATA, PF_ENC_DELTA_BYTE_ARRAY, 5000, 30000, 30000));
-            std::snprintf(name, sizeof name, "4b delta byte array type %d rep %d", pt, rep);
-            run(name, {c}, PfOpts{}, p);
-            const bool tabs = pt != PF_INT32;
-            check((p.pages[0].dx != nullptr) == tabs && (p.pages[0].aux != nullptr) == tabs && p.lists[L_DLEN].size() == size_t(tabs) &&
-                      p.lists[L_DBA].size() == size_t(tabs), "delta byte array tables");
-            check(p.n_decode_first == 1 && p.pages[0].nseg == 0, "delta byte array routing");
-        }
+        for (int rep : {0, 1})
+            for (int nv : {5000, 4095, 4096, 4097}) {
+                Chunk c = chunk(pt, 1 + rep, rep, PF_CODEC_UNCOMPRESSED);
+                c.d.type_length = pt == PF_FIXED_LEN_BYTE_ARRAY ? 7 : 0;
+                c.pages.push_back(page(PF_PAGE_DATA, PF_ENC_DELTA_BYTE_ARRAY, nv, 30000, 30000));
+                std::snprintf(name, sizeof name, "4b delta byte array type %d rep %d, %d values", pt, rep, nv);
+                run(name, {c}, PfOpts{}, p);
+                const bool tabs = pt != PF_INT32;
+                check((p.pages[0].dx != nullptr) == tabs && (p.pages[0].aux != nullptr) == tabs && p.lists[L_DLEN].size() == size_t(tabs) &&
+                          p.lists[L_DBA].size() == size_t(tabs), "delta byte array tables");
+                check(p.n_decode_first == 1 && p.pages[0].nseg == 0, "delta byte array routing");
+            }
     // 5. BYTE_ARRAY dictionary at and above the sticky threshold
     for (uint32_t db : {65536u, 65537u}) {
         Chunk c = chunk(PF_BYTE_ARRAY, 0, 0, PF_CODEC_UNCOMPRESSED);
