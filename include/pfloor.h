@@ -102,7 +102,7 @@ typedef struct pf_chunk_desc {
     int32_t  repeated_def;        /* def level of the innermost REPEATED ancestor (0 if max_rep == 0):
                                      an entry is a list element ("slot") iff def >= repeated_def */
     int32_t  list_null_def;       /* the innermost list is non-null iff def >= list_null_def */
-    int32_t  codec;               /* pf_codec: UNCOMPRESSED, SNAPPY or ZSTD (others: PF_ERR_UNSUPPORTED_CODEC) */
+    int32_t  codec;               /* pf_codec: UNCOMPRESSED, SNAPPY, ZSTD or LZ4_RAW (others: PF_ERR_UNSUPPORTED_CODEC) */
     int32_t  n_pages;             /* pages, including the dictionary page if present */
     const pf_page_desc* pages;
     uint64_t chunk_offset;        /* offset of the chunk's first byte in the bytes buffer */
@@ -307,6 +307,12 @@ int pf_snappy_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst
  * frames are damaged or produce more than cap. Invalidates the results of the last
  * pf_decode_row_group on this context. */
 int pf_zstd_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
+/* Decompress one raw LZ4 block (the LZ4 block format, parquet-format codec LZ4_RAW: no frame, no
+ * length) with the page kernel. The format carries no length, so the block has to produce exactly
+ * size bytes: PF_ERR_CORRUPT_PAGE when it is damaged or produces one byte less or more; offset 0
+ * and an empty src are refused. Host buffers of at most 1 GiB; synchronous. *out_len = size on
+ * success. Invalidates the results of the last pf_decode_row_group on this context. */
+int pf_lz4_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t size, size_t* out_len);
 /* 1 if the last pf_snappy_decompress needed the serial fallback kernel (stream not split into
  * independent 64 KiB blocks, or corrupt), 0 if the block-parallel kernels decoded it. */
 int pf_snappy_last_fallback(pf_ctx* ctx);

@@ -127,6 +127,19 @@ PF_HD inline uint32_t zstd_lit_stride(uint32_t max_dst) {
     return ((max_dst < ZSTD_LIT_MAX ? max_dst : ZSTD_LIT_MAX) + 255u) / 256u * 256u + 256u;
 }
 
+// One LZ4 decompression job (pf_lz4.hip): the raw block src -> exactly dst_len bytes at dst.
+struct Lz4Job {
+    const uint8_t* src;
+    uint8_t* dst;
+    uint32_t src_len;
+    uint32_t dst_len;
+    int32_t page;         // global page index (for error attribution)
+    int32_t chunk;
+    uint32_t produced;    // out: bytes written (0 when the job failed)
+    uint32_t pad;
+};
+constexpr int LZ4_GRID = 2048;                   // most workgroups of k_lz4 (they stride over the jobs)
+
 // DONE_PAGE: k_page_null decoded the whole page (with DONE_NULL); k_lvl and k_flat_null skip only
 // such pages -- never DONE_NULL itself, which k_flat_null's own finished blocks of the page set.
 // DONE_DSTR: k_flat_dstr decoded the page (set together with DONE_FLAT); k_flat_all's blocks of the page return at it.

@@ -22,6 +22,9 @@ void launch_snappy(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int 
 void launch_zstd(ZstdJob* d_jobs, const int* d_order, int n_jobs, uint8_t* d_lit, uint32_t lit_stride, DevChunkResult* d_res,
                  hipStream_t s);
 
+// pf_lz4.hip
+void launch_lz4(Lz4Job* d_jobs, const int* d_order, int n_jobs, DevChunkResult* d_res, hipStream_t s);
+
 // pf_snappy_head.hip
 void launch_snappy_head(SnappyJob* d_jobs, int n_jobs, DevPage* d_pages, const DevChunk* d_chunks, int* d_fb,
                         const DevChunkResult* d_res, hipStream_t st);

@@ -107,7 +107,8 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
     ck.first_page = int(p.pages.size());
     int64_t& hs = p.host_status[size_t(c)];
     if (ck.width < 0) hs = PF_ERR_UNSUPPORTED_TYPE;
-    else if (cd.codec != PF_CODEC_UNCOMPRESSED && cd.codec != PF_CODEC_SNAPPY && cd.codec != PF_CODEC_ZSTD)
+    else if (cd.codec != PF_CODEC_UNCOMPRESSED && cd.codec != PF_CODEC_SNAPPY && cd.codec != PF_CODEC_ZSTD &&
+             cd.codec != PF_CODEC_LZ4_RAW)
         hs = PF_ERR_UNSUPPORTED_CODEC;
     else if (cd.max_def < 0 || cd.max_def > 255 || cd.max_rep < 0 || cd.max_rep > 255 || cd.n_pages < 0 ||
              (cd.n_pages > 0 && !cd.pages) || cd.chunk_offset + cd.chunk_size > n_bytes)
@@ -149,6 +150,11 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                     j.page = int(p.pages.size()); j.chunk = c;
                     j.exact = 1;
                     p.zjobs.push_back(j);
+                } else if (cd.codec == PF_CODEC_LZ4_RAW) {
+                    Lz4Job j{};
+                    j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
+                    j.page = int(p.pages.size()); j.chunk = c;
+                    if (j.src_len || j.dst_len) p.ljobs.push_back(j);   // (an empty section stored as no bytes: nothing to do)
                 } else {
                     SnappyJob j{};
                     j.src_len = pd.compressed_size - lvl; j.dst_len = pd.uncompressed_size - lvl;
@@ -231,6 +237,7 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
         while (int(p.pages.size()) > ck.first_page) { p.pages.pop_back(); p.pplan.pop_back(); }
         while (!p.jobs.empty() && p.jobs.back().chunk == c) p.jobs.pop_back();
         while (!p.zjobs.empty() && p.zjobs.back().chunk == c) p.zjobs.pop_back();
+        while (!p.ljobs.empty() && p.ljobs.back().chunk == c) p.ljobs.pop_back();
         ck.n_pages = 0; ck.dict_page = -1; entries = 0;
     }
     if (ck.dict_page >= 0) ck.first_page = ck.dict_page + 1;
@@ -440,6 +447,13 @@ void plan_zstd(BatchPlan& p) {
     p.off_zlit = take(p.scratch_bytes, size_t(p.zstd_grid) * p.zlit_stride, 256);
 }
 
+// LZ4 jobs: the dispatch order, as for ZSTD (k_lz4 needs no area of its own).
+void plan_lz4(BatchPlan& p) {
+    std::vector<int>& order = p.lists[L_LZ4];
+    for (size_t j = 0; j < p.ljobs.size(); j++) order.push_back(int(j));
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.ljobs[size_t(a)].src_len > p.ljobs[size_t(b)].src_len; });
+}
+
 void plan_meta(BatchPlan& p) {
     size_t m = 0;
     for (int l = 0; l < N_LISTS; l++) p.list_base[l + 1] = p.list_base[l] + p.lists[l].size();
@@ -456,6 +470,7 @@ void plan_meta(BatchPlan& p) {
     p.off_batiles = take(m, sizeof(Int2) * p.ba_tiles.size());
     p.off_nfbq = take(m, 16 + sizeof(Int2) * size_t(p.n_flat_fixed + p.n_null4 + p.n_null8), 16);   // fallback queue
     p.off_zjobs = take(m, sizeof(ZstdJob) * p.zjobs.size());
+    p.off_ljobs = take(m, sizeof(Lz4Job) * p.ljobs.size());
     p.meta_bytes = take(m, 256) + 256;   // arena counter lives in the last 256 bytes
 }
 
@@ -466,7 +481,7 @@ void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const Pf
     p.chunks.assign(size_t(n_chunks), DevChunk{});
     p.host_status.assign(size_t(n_chunks), 0);
     p.oplan.resize(size_t(n_chunks));
-    p.pages.clear(); p.pplan.clear(); p.jobs.clear(); p.zjobs.clear();
+    p.pages.clear(); p.pplan.clear(); p.jobs.clear(); p.zjobs.clear(); p.ljobs.clear();
     p.bajobs.clear(); p.ba_tiles.clear(); p.ba_bm.clear();
     for (auto& l : p.lists) l.clear();
     p.ba_short_dict = p.ba_short_data = true;
@@ -483,6 +498,7 @@ void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const Pf
     plan_routes(opts, p);
     plan_snappy(p.jobs, p.snap);
     plan_zstd(p);
+    plan_lz4(p);
     plan_meta(p);
 }
 
@@ -523,6 +539,11 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
     }
     bind_snappy(p.jobs, p.snap, a.tokmap);
     for (ZstdJob& jb : p.zjobs) {
+        const DevPage& pg = p.pages[size_t(jb.page)];
+        jb.src = at(a.in, p.pplan[size_t(jb.page)].in_off) + pg.rep_len + pg.def_len;
+        jb.dst = at(S, p.pplan[size_t(jb.page)].scratch_off);
+    }
+    for (Lz4Job& jb : p.ljobs) {
         const DevPage& pg = p.pages[size_t(jb.page)];
         jb.src = at(a.in, p.pplan[size_t(jb.page)].in_off) + pg.rep_len + pg.def_len;
         jb.dst = at(S, p.pplan[size_t(jb.page)].scratch_off);

@@ -2,7 +2,7 @@
 // call, no context, not a byte of the input read -- only arithmetic on the descriptors, so the
 // routing of every page can be checked without a GPU (tests/native/pf_plan_check.cpp).
 //
-//   plan_batch  descriptors -> DevChunk / DevPage / SnappyJob / ZstdJob / BaJob tables, the launch lists and
+//   plan_batch  descriptors -> DevChunk / DevPage / SnappyJob / ZstdJob / Lz4Job / BaJob tables, the launch lists and
 //               grids, the arena sizes and the metadata layout. Offsets only.
 //   bind_batch  offsets -> device pointers, given where the runtime allocated the arenas.
 #pragma once
@@ -37,6 +37,7 @@ enum ListId {
     L_NSEG,     // their (page, segment) pairs
     L_CDICT,    // (page, block) pairs of flat dictionary BYTE_ARRAY pages (k_count_dict)
     L_ZSTD,     // ZSTD jobs in dispatch order: the most compressed bytes first (k_zstd)
+    L_LZ4,      // LZ4_RAW jobs in dispatch order: the most compressed bytes first (k_lz4)
     N_LISTS
 };
 
@@ -45,7 +46,7 @@ constexpr uint64_t NO_OFF = ~0ull;
 // Where a page's regions lie (NO_OFF: the page has none).
 struct PagePlan {
     uint64_t in_off;        // the page's first body byte in the input (v2: its levels)
-    uint64_t scratch_off;   // decompressed body (Snappy and ZSTD pages), 16-byte aligned
+    uint64_t scratch_off;   // decompressed body (Snappy, ZSTD and LZ4_RAW pages), 16-byte aligned
     uint64_t aux_off;       // BYTE_ARRAY value positions / ids, DELTA_BINARY_PACKED values, dictionary pos + len
     uint64_t rt_off;        // k_runs table
     uint64_t dx_off;        // k_dlen tables
@@ -90,6 +91,7 @@ struct BatchPlan {
     std::vector<DevPage> pages;
     std::vector<SnappyJob> jobs;
     std::vector<ZstdJob> zjobs;            // ZSTD pages (k_zstd); L_ZSTD is their dispatch order
+    std::vector<Lz4Job> ljobs;             // LZ4_RAW pages (k_lz4); L_LZ4 is their dispatch order
     std::vector<BaJob> bajobs;             // PLAIN BYTE_ARRAY walks: dictionary pages, then data pages
     std::vector<Int2> ba_tiles;            // (job relative to its half, tile)
     SnappyPlan snap;
@@ -111,7 +113,7 @@ struct BatchPlan {
     uint64_t chars_hint = 0;               // uncompressed bytes of the BYTE_ARRAY data pages
     // metadata block; its last 256 bytes hold the chars arena counter
     size_t off_chunks = 0, off_pages = 0, off_jobs = 0, off_lists = 0, off_res = 0, off_pieces = 0, off_splits = 0,
-           off_fallback = 0, off_wins = 0, off_bajobs = 0, off_batiles = 0, off_nfbq = 0, off_zjobs = 0, meta_bytes = 0;
+           off_fallback = 0, off_wins = 0, off_bajobs = 0, off_batiles = 0, off_nfbq = 0, off_zjobs = 0, off_ljobs = 0, meta_bytes = 0;
     std::vector<PagePlan> pplan;           // per page
     std::vector<OutPlan> oplan;            // per chunk
     std::vector<uint64_t> ba_bm;           // per BaJob: its bitmaps and tile counts (scratch)

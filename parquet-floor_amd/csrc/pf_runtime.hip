@@ -5,7 +5,7 @@
 // planner (pf_plan.cpp, no HIP calls) turns the descriptors into flat DevChunk / DevPage /
 // SnappyJob tables, launch lists and arena sizes; this file grows the arenas to those sizes, has
 // the planner bind its offsets to them, uploads the tables in one copy, and enqueues
-//   k_snappy / k_zstd -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
+//   k_snappy / k_zstd / k_lz4 -> k_ba (dictionaries) -> k_delta -> k_count -> k_ba (PLAIN pages) -> k_scan -> k_flat -> k_decode
 // on the context stream. Nothing synchronises until pf_wait, which hands what came down to the host-only result
 // side (pf_result.cpp: side-table layouts, the rerun decision, pf_column_info). The context itself is pf_ctx.h; the
 // write path is a unit of its own, pf_enc_runtime.hip.
@@ -157,6 +157,8 @@ int enqueue_kernels(pf_ctx* ctx) {
     // ZSTD pages (a batch without one enqueues nothing here)
     launch_zstd(reinterpret_cast<ZstdJob*>(meta + p.off_zjobs), list(L_ZSTD), int(p.zjobs.size()),
                 static_cast<uint8_t*>(ctx->d_scratch.p) + p.off_zlit, p.zlit_stride, d_res, st);
+    // LZ4_RAW pages (likewise)
+    launch_lz4(reinterpret_cast<Lz4Job*>(meta + p.off_ljobs), list(L_LZ4), int(p.ljobs.size()), d_res, st);
     EVREC(ctx, ctx->ev[3], st);
     BaJob* d_bajobs = reinterpret_cast<BaJob*>(meta + p.off_bajobs);
     const int2* d_batiles = reinterpret_cast<const int2*>(meta + p.off_batiles);
@@ -237,6 +239,7 @@ int upload_meta(pf_ctx* ctx) {
     put(p.off_pages, p.pages);
     put(p.off_jobs, p.jobs);
     put(p.off_zjobs, p.zjobs);
+    put(p.off_ljobs, p.ljobs);
     put(p.off_pieces, p.snap.pieces);
     std::memset(h + p.off_splits, 0xff, sizeof(uint32_t) * p.snap.n_splits);
     put(p.off_wins, p.snap.wins);
@@ -869,7 +872,7 @@ int pf_sync(pf_ctx* ctx) {
 }
 
 namespace {
-// The head of a one-shot call (Snappy, ZSTD, page scan): the arenas may be reallocated below, so this context's pending
+// The head of a one-shot call (Snappy, ZSTD, LZ4, page scan): the arenas may be reallocated below, so this context's pending
 // copies out of them finish first. drop_batch: d_meta will hold this call's layout, the last decode's tables are gone.
 int begin_oneshot(pf_ctx* ctx, bool drop_batch) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -985,6 +988,45 @@ int pf_zstd_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, 
     std::memcpy(&done, hr, sizeof done);
     const DevChunkResult* r = reinterpret_cast<const DevChunkResult*>(hr + o_res);
     if (r->status != 0) return fail(ctx, r->status, "zstd: corrupt input");
+    if (done.produced) HIPCHK(ctx, hipMemcpy(dst, ctx->d_scratch.p, done.produced, hipMemcpyDeviceToHost));
+    *out_len = done.produced;
+    return PF_OK;
+}
+
+// One raw LZ4 block through k_lz4 (pf_lz4.hip), as one job that has to produce exactly size bytes.
+int pf_lz4_decompress(pf_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t size, size_t* out_len) {
+    if (!ctx || (!src && n) || (!dst && size) || !out_len) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+    if (n > (1ull << 30) || size > (1ull << 30)) return fail(ctx, PF_ERR_INVALID_ARG, "lz4: buffer too large");
+    *out_len = 0;
+    if (const int rc = begin_oneshot(ctx, true)) return rc;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, ctx->d_in.ensure(std::max<size_t>(n, 1)));
+    HIPCHK(ctx, ctx->d_scratch.ensure(size + 16));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_in.p, src, n, hipMemcpyHostToDevice, st));
+    Lz4Job job{};
+    job.src = static_cast<const uint8_t*>(ctx->d_in.p);
+    job.dst = static_cast<uint8_t*>(ctx->d_scratch.p);
+    job.src_len = uint32_t(n);
+    job.dst_len = uint32_t(size);
+    const size_t o_res = 256, m = 512;
+    HIPCHK(ctx, ctx->d_meta.ensure(m));
+    HIPCHK(ctx, ctx->h_meta.ensure(m));
+    HIPCHK(ctx, ctx->h_res.ensure(512));
+    uint8_t* h = static_cast<uint8_t*>(ctx->h_meta.p);
+    std::memset(h, 0, m);
+    std::memcpy(h, &job, sizeof job);
+    uint8_t* d = static_cast<uint8_t*>(ctx->d_meta.p);
+    HIPCHK(ctx, hipMemcpyAsync(d, h, m, hipMemcpyHostToDevice, st));
+    launch_lz4(reinterpret_cast<Lz4Job*>(d), nullptr, 1, reinterpret_cast<DevChunkResult*>(d + o_res), st);
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t* hr = static_cast<uint8_t*>(ctx->h_res.p);
+    HIPCHK(ctx, hipMemcpyAsync(hr, d, m, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    Lz4Job done;
+    std::memcpy(&done, hr, sizeof done);
+    const DevChunkResult* r = reinterpret_cast<const DevChunkResult*>(hr + o_res);
+    if (r->status != 0) return fail(ctx, r->status, "lz4: corrupt input");
     if (done.produced) HIPCHK(ctx, hipMemcpy(dst, ctx->d_scratch.p, done.produced, hipMemcpyDeviceToHost));
     *out_len = done.produced;
     return PF_OK;

@@ -179,6 +179,7 @@ def _load(path):
         "pf_last_timing": ([vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)], C.c_int),
         "pf_snappy_decompress": ([vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)], C.c_int),
         "pf_zstd_decompress": ([vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)], C.c_int),
+        "pf_lz4_decompress": ([vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)], C.c_int),
         "pf_snappy_last_fallback": ([vp], C.c_int),
         "pf_scan_pages": ([vp, C.POINTER(ScanChunk), i32, vp, sz, i32, i32, C.POINTER(PageDesc),
                            C.POINTER(ScanResult)], C.c_int),

@@ -502,6 +502,18 @@ class GpuDecoder:
             return rc
         return dst[:size].tobytes() if out_len.value == size else -2
 
+    def lz4_decompress(self, data: bytes, size: int):
+        """One raw LZ4 block (codec LZ4_RAW) -> bytes on the GPU (k_lz4). size: the uncompressed length, as a
+        page header states it. Returns the bytes, or a negative status: -2 when the block is damaged or
+        does not produce exactly size bytes."""
+        src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+        out_len = C.c_size_t()
+        dst = np.zeros(max(1, size), dtype=np.uint8)
+        rc = lib().pf_lz4_decompress(self.h, src.ctypes.data, len(data), dst.ctypes.data, size, C.byref(out_len))
+        if rc != 0:
+            return rc
+        return dst[:size].tobytes() if out_len.value == size else -2
+
     def zstd_compress(self, data: bytes, cap=None):
         """bytes -> one ZSTD frame, compressed on the GPU (k_zstd_compress). Returns the frame, or a negative
         status (-6: cap is too small). cap: the destination's size (default: what always suffices)."""
