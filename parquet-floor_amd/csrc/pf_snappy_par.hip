@@ -1508,21 +1508,32 @@ __global__ __launch_bounds__(64) void k_snappy_exec2(const SnappyJob* __restrict
 #endif
 constexpr uint32_t X5_BATCH = PF_X5_BATCH;                     // output bytes of one batch (ring: + XSLOT + far margin)
 constexpr uint32_t X5_STG = (XSTAGE + 15u) & ~15u;     // one staged input chunk
-constexpr uint32_t X5_FSLOT = 80u;                     // a far copy's source: 5 aligned 16-byte chunks (<= 64 B + shift < 16)
-constexpr uint32_t X5_FSL = XFAR * X5_FSLOT;           // far-copy source slots of one batch
-constexpr uint32_t X5_STAGE0 = XRING;                  // [ring | stage x2 | far slots x2]: one byte address
-constexpr uint32_t X5_LDS = XRING + 2u * X5_STG;       // selects any byte source (the far slots: their own array)
+// Far-copy sources of a batch, packed by 16-byte chunk. A far copy of ol bytes whose source's global address
+// has the low four bits fsh takes the nch = (fsh + ol + 15) >> 4 aligned chunks that cover it (1..5: ol <= 64,
+// fsh < 16), at chunks [cb, cb + nch) of the batch's buffer, cb the sum of nch over the batch's earlier far
+// copies in token order. Chunk cb + i holds the 16 bytes at (source address - fsh) + 16 i, so source byte j is
+// buffer byte 16 cb + fsh + j. The consumer reads a far copy's byte j < ol only, through descriptor word 1
+// (below), and fsh + j < fsh + ol <= 16 nch: every byte it reads lies in a chunk this copy loaded. Chunks past
+// the batch's total are not loaded and keep stale bytes; no descriptor points at them. A batch is cut before the
+// far copy whose chunks would pass X5_FCH.
+#ifndef PF_X5_FCH
+#define PF_X5_FCH 64
+#endif
+constexpr uint32_t X5_FCH = PF_X5_FCH;                 // far-copy source chunks of one batch
+constexpr uint32_t X5_FSL = X5_FCH * 16u;              // their bytes (first the chunk address table, then the chunks)
+constexpr uint32_t X5_STAGE0 = XRING;                  // [ring | stage x2 | far chunks x2]: one byte address
+constexpr uint32_t X5_LDS = XRING + 2u * X5_STG;       // selects any byte source (the far chunks: their own array)
 constexpr uint32_t X5_W = 768u / 32u;                  // token-start words of a batch (+ its alignment bytes)
 constexpr uint32_t X5_LINE = 128u;                     // a far source's cache line must be wholly landed
-constexpr uint32_t X5_FREAD = 5u * 16u;                // bytes a far load reads from its 16-byte aligned base
 #ifndef PF_X5_TPL
 #define PF_X5_TPL 2
 #endif
 constexpr int X5_TPL = PF_X5_TPL;                      // tokens a producer lane decodes per batch
 constexpr uint32_t X5_DS = 64u * X5_TPL + 1u;          // descriptor table: entry t at [t], its second word at [t + X5_DS]
 static_assert(X5_BATCH + 3u <= 768u, "a batch and its alignment bytes are at most three 256-byte windows");
-static_assert((X5_FSLOT & 15u) == 0u, "far slots are 16-byte aligned");
-static_assert(5u * XFAR <= 128u, "a batch's far-copy chunks are loaded by two LDS-DMA wave instructions");
+static_assert(X5_FCH <= 128u, "a batch's far-copy chunks are loaded by at most two LDS-DMA wave instructions");
+static_assert(X5_FCH >= 32u && (X5_FCH > 64u ? 128u : 64u) * 8u <= X5_FSL && (X5_FCH + 4u) * 8u <= X5_FSL,
+              "the chunk address table (an entry per loading lane, and four past the last chunk) lies inside one batch's chunk bytes");
 enum : uint32_t { R5_NORMAL = 0, R5_LONG = 1, R5_NOP = 2, R5_END = 3, R5_BAD = 4 };
 // Descriptor word 0: the token's first output byte relative to the batch's 4-byte aligned base S
 // (bits 0-15); a copy whose source is read through the ring / the window: its offset (< 4 KiB) in bits
@@ -1622,7 +1633,7 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
     auto& REC = S.REC;
     uint8_t* const jvb = reinterpret_cast<uint8_t*>(S.jv);
     uint8_t* const ring = L;
-    // The far-copy slots are a separate LDS array, so the compiler can tell the producer's LDS-DMA from its
+    // The far-copy chunks are a separate LDS array, so the compiler can tell the producer's LDS-DMA from its
     // other LDS accesses (one array: it waits for the loads before the first descriptor write); the
     // consumer reaches them through the same byte address as the ring and stage, relative to L.
     const uint32_t Lb = uint32_t(reinterpret_cast<uintptr_t>(L));   // (a flat LDS address's low half: the LDS offset)
@@ -1792,10 +1803,10 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                 if (__any(wrong) || nt == 0) {
                     ok = false;
                 } else {
-                    uint32_t kd[X5_TPL], off[X5_TPL], srcv[X5_TPL], a[X5_TPL], frank[X5_TPL];
-                    bool farc[X5_TPL], fnr[X5_TPL], lstaged[X5_TPL];
-                    unsigned long long farm[X5_TPL], cutm[X5_TPL];
-                    uint32_t fbase = 0;
+                    uint32_t kd[X5_TPL], off[X5_TPL], srcv[X5_TPL], a[X5_TPL], fsh[X5_TPL], nch[X5_TPL], fce[X5_TPL];
+                    bool farc[X5_TPL], fnr[X5_TPL], lstaged[X5_TPL], fdd[X5_TPL];
+                    unsigned long long cutm[X5_TPL], farm = 0;
+                    unsigned long long wide2 = 0, wide4 = 0;   // far copies of >= 2 / >= 4 chunks among the tokens
                     #pragma unroll
                     for (int h = 0; h < X5_TPL; h++) {
                         kd[h] = tk[h].kind;
@@ -1805,14 +1816,58 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                         a[h] = otok[h] - off[h];          // copy source start
                         farc[h] = take[h] && kd[h] != 0 && a[h] + min(ol[h], off[h]) <= op &&
                                   int32_t(a[h] - (op + X5_BATCH - XRING)) < 0;
-                        // source not yet landed in HBM: every cache line its 80-byte aligned read touches must be
-                        fnr[h] = farc[h] && a[h] + X5_FREAD + X5_LINE > LF;
-                        farm[h] = __ballot(farc[h]);
-                        frank[h] = fbase + uint32_t(__popcll(farm[h] & lane_mask_lt(uint32_t(lane))));
-                        fbase += uint32_t(__popcll(farm[h]));
-                        cutm[h] = __ballot(take[h] && (ol[h] > 64u || inc[h] > X5_BATCH || (kd[h] == 0 && !lstaged[h]) ||
-                                                       (farc[h] && frank[h] >= XFAR) || fnr[h]));
+                        // Source not yet landed in HBM: every cache line an issued load touches must lie wholly
+                        // below the landed frontier LF. The copy's loads read addresses [A - fsh, A - fsh + 16 nch),
+                        // A = arena + a the source's address. They end at output offset
+                        // a - fsh + 16 nch <= a + ol + 15 (16 nch <= fsh + ol + 15), at a 16-byte aligned address,
+                        // so at most X5_LINE - 16 bytes of the last cache line lie behind them: the highest line
+                        // touched ends at or below output offset a + ol + 15 + X5_LINE - 16 of the same arena,
+                        // whatever the arena's base alignment is (the scratch body and the column arena of a
+                        // direct page are aligned differently, and neither as the output offset). Landed when
+                        // that is <= LF; lines below the last are older still. (Bytes of a line that lie outside
+                        // this piece's output, or in the scratch body past od.dlo, are never a far copy's source.)
+                        fnr[h] = farc[h] && a[h] + ol[h] + (X5_LINE - 1u) > LF;
+                        farm |= __ballot(farc[h]);
+                        fsh[h] = 0u;
+                        nch[h] = 0u;
+                        fce[h] = 0u;
+                        fdd[h] = false;
                     }
+                    if (farm) {   // (a batch without far copies skips this)
+                        // (the low bits of the two arenas' addresses: a source's alignment to its 16-byte chunks)
+                        const uint32_t dst_lo = uint32_t(reinterpret_cast<uintptr_t>(gdst)) & 15u;
+                        const uint32_t dd_lo = uint32_t(reinterpret_cast<uintptr_t>(od.dd)) & 15u;
+                        uint32_t anyn = 0;
+                        #pragma unroll
+                        for (int h = 0; h < X5_TPL; h++) {
+                            // the address the source is read from: the column arena from od.dlo on, else the scratch body
+                            fdd[h] = od.dd != nullptr && a[h] >= od.dlo;
+                            fsh[h] = ((fdd[h] ? dd_lo : dst_lo) + a[h]) & 15u;
+                            nch[h] = farc[h] ? (fsh[h] + ol[h] + 15u) >> 4 : 0u;
+                            anyn |= nch[h];
+                        }
+                        wide2 = __ballot(anyn > 1u);
+                        wide4 = __ballot(anyn > 3u);
+                        // chunk base: the exclusive prefix of nch in token order (fce: the inclusive one). One DPP
+                        // scan for two halves of the lanes, 16 bits each (a half's sum is at most 5 * 64)
+                        uint32_t cbase = 0;
+                        #pragma unroll
+                        for (int h = 0; h < X5_TPL; h += 2) {
+                            const int h1 = h + 1 < X5_TPL ? h + 1 : h;   // (the pair's second half, if there is one)
+                            const uint32_t sc = dpp_incl_scan(nch[h] | (h1 != h ? nch[h1] << 16 : 0u));
+                            const uint32_t tot = __builtin_amdgcn_readlane(sc, 63);
+                            fce[h] = cbase + (sc & 0xffffu);
+                            cbase += tot & 0xffffu;
+                            if (h1 != h) {
+                                fce[h1] = cbase + (sc >> 16);
+                                cbase += tot >> 16;
+                            }
+                        }
+                    }
+                    #pragma unroll
+                    for (int h = 0; h < X5_TPL; h++)
+                        cutm[h] = __ballot(take[h] && (ol[h] > 64u || inc[h] > X5_BATCH || (kd[h] == 0 && !lstaged[h]) ||
+                                                       (farc[h] && fce[h] > X5_FCH) || fnr[h]));
                     uint32_t cut = uint32_t(nt);
                     #pragma unroll
                     for (int h = X5_TPL - 1; h >= 0; h--)
@@ -1834,10 +1889,13 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                     } else {
                         used = cut;
                         const uint32_t ch = (cut - 1u) >> 6;   // the half holding the batch's last token
-                        uint32_t btot = 0;
+                        uint32_t btot = 0, ntot = 0;   // the batch's output bytes and far-copy chunks
                         #pragma unroll
                         for (int h = 0; h < X5_TPL; h++)
-                            if (ch == uint32_t(h)) btot = __builtin_amdgcn_readlane(inc[h], (cut - 1u) & 63u);
+                            if (ch == uint32_t(h)) {
+                                btot = __builtin_amdgcn_readlane(inc[h], (cut - 1u) & 63u);
+                                ntot = __builtin_amdgcn_readlane(fce[h], (cut - 1u) & 63u);
+                            }
                         bool inb[X5_TPL], lit[X5_TPL], cp[X5_TPL], far[X5_TPL];
                         bool bad = false;
                         #pragma unroll
@@ -1853,33 +1911,45 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                         if (__any(bad)) ok = false;
                         X5T(1);   // token decode, chain checks, cuts
                         if (ok) {
-                            uint32_t fsh[X5_TPL];
-                            uint32_t nfar = 0;
-                            uint64_t* fa = reinterpret_cast<uint64_t*>(FS + b * X5_FSL);   // (overwritten by the loads)
-                            #pragma unroll
-                            for (int h = 0; h < X5_TPL; h++) {
-                                const PF_GLOBAL uint8_t* fb0 = od.dd != nullptr && a[h] >= od.dlo ? od.dd + a[h] : gdst + a[h];
-                                fsh[h] = uint32_t(reinterpret_cast<uintptr_t>(fb0) & 15u);
-                                if (far[h]) fa[frank[h]] = reinterpret_cast<uintptr_t>(fb0) & ~uintptr_t(15);
-                                nfar += uint32_t(__popcll(farm[h] & lane_mask_lt(cut > 64u * uint32_t(h) ? cut - 64u * uint32_t(h) : 0u)));
-                            }
-                            // far-copy sources: five aligned 16-byte chunks each (the arenas keep >= 80 bytes of
-                            // slack), loaded straight into the slots by LDS-DMA -- lane l loads chunk l % 5 of far
-                            // copy l / 5, so the lane-linear destination is the slot layout -- and waited for only
-                            // before the barrier, after the descriptors (no data registers, latency behind them)
-                            if (nfar) {
-                                x5_order();
-                                const uint32_t l0 = uint32_t(lane), f0 = (l0 * 205u) >> 10;   // l / 5 for l < 128
-                                const uint64_t s0a = fa[f0] + 16u * (l0 - 5u * f0);
-                                uint64_t s1a = 0;
-                                if (nfar > 12u) {
-                                    const uint32_t l1 = l0 + 64u, f1 = (l1 * 205u) >> 10;
-                                    s1a = fa[min(f1, XFAR - 1u)] + 16u * (l1 - 5u * f1);
+                            // far-copy sources: each copy's lane writes the addresses of its nch aligned chunks
+                            // (which end with the chunk holding the source's last byte, inside the arena) into
+                            // the batch's chunk address table, at its chunk base on; then lane l loads chunk l
+                            // (and 64 + l) straight into the chunk buffer by LDS-DMA, so the lane-linear destination
+                            // is the packed layout. The table lies in the bytes the loads overwrite: both table
+                            // reads are issued before the first load. The loads are waited for only before the
+                            // barrier, after the descriptors (no data registers, latency behind them).
+                            if (ntot) {
+                                uint64_t* ca = reinterpret_cast<uint64_t*>(FS + b * X5_FSL);
+                                uint64_t fb0v[X5_TPL];
+                                #pragma unroll
+                                for (int h = 0; h < X5_TPL; h++) {
+                                    const uint64_t fb0 = reinterpret_cast<uintptr_t>((fdd[h] ? od.dd : gdst) + a[h]) & ~uintptr_t(15);
+                                    fb0v[h] = fb0;
                                 }
-                                uint8_t* slots = FS + b * X5_FSL;
-                                const uint32_t sl0 = __builtin_amdgcn_readfirstlane(uint32_t(reinterpret_cast<uintptr_t>(slots)));
-                                if (l0 < 5u * nfar) x5_dma16(s0a, sl0);
-                                if (nfar > 12u && l0 + 64u < 5u * nfar) x5_dma16(s1a, sl0 + 1024u);
+                                // Every far copy writes entries cb0 .. cb0 + 4 (up to cb0 + 2, or cb0 alone, when no copy
+                                // among the tokens takes more chunks than that), the highest first: an entry past a copy's own nch belongs to a later copy, which writes it with a
+                                // smaller i, so later (one wave's LDS operations run in order), and the right address
+                                // stays. cb0 + 4 < X5_FCH + 4 entries: inside the batch's chunk bytes (8 (X5_FCH + 4) <=
+                                // 16 X5_FCH); entries at or past the batch's total are not used.
+                                #pragma unroll
+                                for (int i = 4; i >= 0; i--) {
+                                    if ((i >= 3 && !wide4) || (i >= 1 && !wide2)) continue;
+                                    #pragma unroll
+                                    for (int h = 0; h < X5_TPL; h++)
+                                        if (far[h]) ca[fce[h] - nch[h] + uint32_t(i)] = fb0v[h] + 16u * uint32_t(i);
+                                }
+                                x5_order();
+                                const uint32_t l0 = uint32_t(lane);
+                                uint64_t s0a = ca[l0];   // (entries at or past ntot: stale, not used)
+                                uint64_t s1a = 0;
+                                if constexpr (X5_FCH > 64u)
+                                    if (ntot > 64u) s1a = ca[64u + l0];
+                                asm volatile("" : "+v"(s0a), "+v"(s1a) :: "memory");   // both reads before the first load
+                                uint8_t* chunks = FS + b * X5_FSL;
+                                const uint32_t sl0 = __builtin_amdgcn_readfirstlane(uint32_t(reinterpret_cast<uintptr_t>(chunks)));
+                                if (l0 < ntot) x5_dma16(s0a, sl0);
+                                if constexpr (X5_FCH > 64u)
+                                    if (ntot > 64u && l0 + 64u < ntot) x5_dma16(s1a, sl0 + 1024u);
                             }
                             X5T(2);   // far-copy source loads (issued)
                             if (lane < int(X5_W)) SB[b][lane] = 0;
@@ -1892,7 +1962,7 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                                     d0 = relS | (near ? (X5_CP | (off[h] << 16)) : 0u);
                                     d1 = near ? uint32_t(65536.0f * __builtin_amdgcn_rcpf(float(off[h]))) + 1u
                                               : (lit[h] ? stg_off + woff + (srcv[h] - I) - relS
-                                                        : FSB + b * X5_FSL + frank[h] * X5_FSLOT + fsh[h] - relS);
+                                                        : FSB + b * X5_FSL + 16u * (fce[h] - nch[h]) + fsh[h] - relS);
                                 }
                                 D[b][1 + 64 * h + lane] = d0;
                                 D[b][1 + X5_DS + 64 * h + lane] = d1;
@@ -1925,7 +1995,7 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
                 REC[b][2] = b_tot;
                 REC[b][3] = b_s0;
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // far-copy slots landed in LDS
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // far-copy chunks landed in LDS
             X5T(3);   // descriptors, token-start words, far-copy loads landed
             k_m2 = k_m1;
             k_m1 = kind;
@@ -2060,7 +2130,7 @@ __device__ __forceinline__ void exec5_piece(X5Lds& S, uint8_t* FS, const SnappyJ
 __global__ __launch_bounds__(128) void k_snappy_exec5(const SnappyJob* __restrict__ jobs, const int2* __restrict__ pieces,
                                                       const uint32_t* __restrict__ splits, int* __restrict__ fb, int mode) {
     __shared__ X5Lds S;
-    __shared__ __attribute__((aligned(16))) uint8_t FS[2 * X5_FSL];   // far-copy source slots of two batches
+    __shared__ __attribute__((aligned(16))) uint8_t FS[2 * X5_FSL];   // far-copy source chunks of two batches
     exec5_piece(S, FS, jobs, pieces, splits, fb, mode, int(blockIdx.x));
 }
 
