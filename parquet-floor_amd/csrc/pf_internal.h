@@ -26,7 +26,8 @@ struct Int2 {
 // environment variables once per context, at pf_ctx_create: A/B selectors for the tools and the
 // switches tests use to force rare paths (forced fallbacks, segment lengths, skipped stages).
 struct PfOpts {
-    int exec = 5;             // PF_EXEC: block-parallel Snappy executor: 5 producer / consumer | 2 one wave
+    int exec = 5;             // PF_EXEC: block-parallel Snappy executor: 5 producer / consumer (pf_snappy_exec.hip) |
+                              // 2 one wave (pf_snappy_exec2.hip, diagnostics build only)
     bool ba_fused = true;     // PF_BA_FUSED=0: the round-3 PLAIN BYTE_ARRAY walk kernels
     bool page_null = false;   // PF_PAGE_NULL=1: k_page_null before k_lvl
     int null_stagger = 0;     // PF_DEBUG_NULL_STAGGER=k: k_flat_null's blocks > 0 wait k rounds (race tests)

@@ -8,7 +8,8 @@
 
 namespace pf {
 
-// pf_snappy.hip, pf_snappy_par.hip
+// pf_snappy.hip (launch_snappy_serial), pf_snappy_parse.hip (launch_snappy_parse), pf_snappy_exec.hip
+// (launch_snappy_exec, launch_snappy), pf_snappy_exec2.hip (launch_snappy_exec2, diagnostics build)
 void launch_snappy_serial(const SnappyJob* d_jobs, int n_jobs, const int* d_fallback, DevChunkResult* d_res, hipStream_t s);
 void launch_snappy_parse(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int n_wins, SnapWin* d_win, SnapEnt* d_ent,
                          uint32_t* d_lane_out, uint32_t* d_splits, int* d_fb, int max_nwin, hipStream_t s);
@@ -17,6 +18,10 @@ void launch_snappy_exec(const SnappyJob* d_jobs, int n_jobs, const int2* d_piece
 void launch_snappy(const SnappyJob* d_jobs, int n_jobs, const int2* d_wins, int n_wins, SnapWin* d_win, SnapEnt* d_ent,
                    uint32_t* d_lane_out, const int2* d_pieces, int n_pieces, uint32_t* d_splits, int* d_fb,
                    DevChunkResult* d_res, int max_nwin, int exec, hipStream_t s);
+#ifdef PF_DIAG
+void launch_snappy_exec2(const SnappyJob* d_jobs, int n_jobs, const int2* d_pieces, int n_pieces, const uint32_t* d_splits,
+                         int* d_fb, hipStream_t s);
+#endif
 
 // pf_zstd.hip
 void launch_zstd(ZstdJob* d_jobs, const int* d_order, int n_jobs, uint8_t* d_lit, uint32_t lit_stride, DevChunkResult* d_res,

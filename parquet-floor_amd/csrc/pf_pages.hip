@@ -33,16 +33,9 @@ namespace pf {
 // Phase stamps of -DPF_STAMPS builds (tools/probe_flat_all.py, tools/probe_wide.py): cycle sums
 // per slot. A __device__ array belongs to one unit, so only this unit's kernels stamp.
 #ifdef PF_STAMPS
-__device__ unsigned long long pf_pstamps[16];
+#include "pf_stamps.h"   // (a macro only: nothing of it lands in this namespace)
+PF_STAMP_TABLE(pf_pstamps, 16, pf_debug_pstamps)
 #define PSTAMP(i, v) atomicAdd(&pf_pstamps[i], (unsigned long long)(v))
-extern "C" int pf_debug_pstamps(unsigned long long* out, int n, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pf_pstamps), sizeof(unsigned long long) * (n < 16 ? n : 16)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(pf_pstamps), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
 #else
 #define PSTAMP(i, v) ((void)0)
 #endif

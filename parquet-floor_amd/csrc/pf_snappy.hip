@@ -19,7 +19,7 @@
 //  * a workgroup barrier (release/acquire at workgroup scope) between tokens makes every lane's
 //    stores visible to the next token's loads.
 // This serial kernel is the FALLBACK: it only runs for pages the block-parallel path
-// (pf_snappy_par.hip) could not decode (corrupt streams — it produces the precise error status).
+// (pf_snappy_parse.hip, pf_snappy_exec.hip) could not decode (corrupt streams — it produces the precise error status).
 // It is launched on every batch and nearly always finds nothing to do, so it holds almost no LDS:
 // a launch that needs a large LDS allocation waits for CUs the other contexts' kernels occupy.
 #include <hip/hip_runtime.h>

@@ -2,7 +2,7 @@
 //
 // parquet-mr 1.12.2 hands every compressed page to snappy-java (DecompressorStream.java:101-173),
 // whatever the stream holds. These two
-// kernels run before the parse kernels (pf_snappy_par.hip) and take the streams that are literals
+// kernels run before the parse kernels (pf_snappy_parse.hip) and take the streams that are literals
 // only; they read the page descriptors (DevPage / DevChunk) and the level section (pf_pages.h),
 // which is why they are a unit of the page decode and not of the Snappy parser.
 //

@@ -378,7 +378,7 @@ def _grammar():
         for n in lens:
             s.lit(s.rand(n), nb=nb).copy(1, 1, 4)
         out.append(_case(f"a.lit_wide_nb{nb}", s))
-    # a 4-byte length field: walk_tok (pf_snappy_par.hip, "nb >= 4u ? 0xffffffffu") breaks the chain on
+    # a 4-byte length field: walk_tok (pf_snappy_parse.hip, "nb >= 4u ? 0xffffffffu") breaks the chain on
     # purpose, the index pass marks the page FB_SERIAL and the serial kernel decodes it.
     for n in (1, 300):
         s = Stream(20 + n)

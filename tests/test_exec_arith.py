@@ -1,4 +1,4 @@
-"""CPU check of the executor consumer's integer source arithmetic (pf_snappy_par.hip, k_snappy_exec5;
+"""CPU check of the executor consumer's integer source arithmetic (pf_snappy_exec.hip, k_snappy_exec5;
 DESIGN 4.25): a copy byte at index j < 64 of a token with offset o < 4096 reads x - o * (1 + floor(j / o)),
 and the consumer takes floor(j / o) as (j * m) >> 16 with m = floor(65536 * rcp(o)) + 1, where the
 hardware reciprocal may round up by an ulp: m is floor(65536 / o) + 1 or one more. Both must be exact."""

@@ -1,4 +1,4 @@
-"""k_snappy_exec5's chunk-packed far-copy sources (pf_snappy_par.hip: X5_FCH), on hand-assembled
+"""k_snappy_exec5's chunk-packed far-copy sources (pf_snappy_exec.hip: X5_FCH), on hand-assembled
 streams (snappy_tokens.Stream). A far copy's source left the 4 KiB ring and is read from HBM: the producer
 loads the nch = (fsh + ol + 15) >> 4 aligned 16-byte chunks that cover it (fsh: the source address's low four
 bits) into the batch's chunk buffer, at the running sum of nch, and cuts the batch before the copy whose chunks
@@ -30,7 +30,7 @@ from test_gpu_snappy_pages import (DIRECT_VALUES, FB_OK, FB_REDO, NV_OPT, _compr
 
 pytestmark = pytest.mark.gpu
 
-X5_FCH = 64           # pf_snappy_par.hip (today's value: a retune moves the cases with it)
+X5_FCH = 64           # pf_snappy_exec.hip (today's value: a retune moves the cases with it)
 PREFIX = 8192         # random literal bytes in front: the sources
 SEP = 1100            # separator literal: > XCHUNK, so the next token opens an input chunk and a batch
 FAR = 5000            # far offsets are FAR .. FAR + 15 (> XRING + X5_BATCH)

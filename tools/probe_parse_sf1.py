@@ -1,5 +1,5 @@
 """Diagnostic (stamps build: PFLOOR_LIB_PATH=parquet-floor_amd/diag/libpfloor_stamps.so): the Snappy parse
-kernels' phase counters (pf_debug_cstamps, CSTAMP slots of pf_snappy_par.hip) for one lineitem row group
+kernels' phase counters (pf_debug_cstamps, CSTAMP slots of pf_snappy_parse.hip) for one lineitem row group
 (all 16 columns in one batch): index pass per window, chain pass per page."""
 import ctypes as C
 import os
