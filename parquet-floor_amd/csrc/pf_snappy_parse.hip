@@ -15,12 +15,13 @@
 //                   lane to lane from the window entry; a lane whose true entry is not on its
 //                   guessed chain re-walks from it, until the chain is consistent (each round
 //                   fixes at least the first wrong lane). Output: the token-start bitmap (1 bit per
-//                   input byte), per-lane output byte counts, the window exit, and an entry
-//                   table: for each entry d < 64 bytes into the window, where the chain from
-//                   W0 + d meets the window's chain and the output difference up to there.
-//   k_snappy_chain  one wave per page. Window w's true entry is window w-1's exit: one table
-//                   lookup per window (a walk in HBM for entries deeper than 64 bytes, an exact
-//                   whole-wave parse for windows the table does not resolve), repeated until the
+//                   input byte), per-lane output byte counts, the window exit X, and the
+//                   successor record: where the chain from X meets the next window's own chain
+//                   (the chain from its start) and the output difference up to there, found by
+//                   a two-pointer walk over IDX_EXT staged bytes past the window end.
+//   k_snappy_chain  one wave per page. Window w's true entry is window w-1's exit: one record
+//                   load per window (a walk in HBM for an entry the record does not answer, an
+//                   exact whole-wave parse for windows neither resolves), repeated until the
 //                   entries are consistent. Output: each window's true entry, merge point or exit,
 //                   output bytes and WM_* mode.
 //   k_snappy_repair one wave per window whose true entry is not its own chain's start: the bitmap
@@ -41,7 +42,7 @@ namespace pf {
 
 // Phase stamps of the parse kernels (tools/probe_parse_sf1.py).
 #ifdef PF_STAMPS
-PF_STAMP_TABLE(pf_cstamps, 32, pf_debug_cstamps)
+PF_STAMP_TABLE(pf_cstamps, 40, pf_debug_cstamps)
 #define CSTAMP(i, v) atomicAdd(&pf_cstamps[i], (unsigned long long)(v))
 #else
 #define CSTAMP(i, v) ((void)0)
@@ -143,13 +144,9 @@ __device__ __forceinline__ uint64_t stage_tok(const uint8_t* stage, uint32_t a, 
     return t.tl;
 }
 
-// The token at stream position p of a linear stage (base = stage offset of position 0): the tag and the 3
-// bytes after it from one aligned dword pair; straight-line lengths (a literal length field of 4 bytes,
-// >= 16 MiB, cannot be in a page: tl = 0xffffffff breaks the chain).
-__device__ __forceinline__ void walk_tok(const uint8_t* stage, uint32_t base, uint32_t p, uint32_t& ol, uint32_t& tl) {
-    const uint32_t a = base + p;
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(stage + (a & ~3u));
-    const uint32_t v = __builtin_amdgcn_alignbyte(w[1], w[0], a & 3u);
+// Output / input bytes of the token whose tag and the 3 bytes after it are v: straight-line lengths (a literal
+// length field of 4 bytes, >= 16 MiB, cannot be in a page: tl = 0xffffffff breaks the chain).
+__device__ __forceinline__ void tok_lens(uint32_t v, uint32_t& ol, uint32_t& tl) {
     const uint32_t tag = v & 0xffu, kind = tag & 3u, Lv = tag >> 2;
     const uint32_t nb = Lv >= 60u ? Lv - 59u : 0u;
     const uint32_t lit_ol = (Lv < 60u ? Lv : ((v >> 8) & ((1u << (8u * min(nb, 3u))) - 1u))) + 1u;
@@ -159,6 +156,14 @@ __device__ __forceinline__ void walk_tok(const uint8_t* stage, uint32_t base, ui
     const uint32_t cp_ol = ((4u + (Lv & 7u)) & m1) | ((Lv + 1u) & ~m1);
     tl = (lit_tl & mlit) | (((0x05030200u >> (8u * kind)) & 0xffu) & ~mlit);
     ol = (lit_ol & mlit) | (cp_ol & ~mlit);
+}
+
+// The token at stream position p of a linear stage (base = stage offset of position 0): the tag and the 3
+// bytes after it from one aligned dword pair.
+__device__ __forceinline__ void walk_tok(const uint8_t* stage, uint32_t base, uint32_t p, uint32_t& ol, uint32_t& tl) {
+    const uint32_t a = base + p;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(stage + (a & ~3u));
+    tok_lens(__builtin_amdgcn_alignbyte(w[1], w[0], a & 3u), ol, tl);
 }
 
 // Walk the chain from c while positions stay below re (bits relative to rs). The token-start bits are
@@ -258,51 +263,78 @@ __device__ uint32_t win_parse_spec(const uint8_t* stage, uint32_t woff, uint32_t
     return X;
 }
 
-// Entry table (index pass -> chain pass): for an entry e = W0 + d, d < 64, where the chain from e
-// meets the window's own chain (bitmap) and the output difference up to that point.
-constexpr int ENT_STEPS = 384;       // longer walks are left to the chain pass (exact lane-region parse)
+// Successor record (index pass -> chain pass). The chain pass asks, for window w + 1, where the chain from
+// its true entry e meets the window's own chain (the one from its start W1) and what the two chains' outputs
+// differ by up to there. Its first guess for e is window w's own exit X, usually the final answer, so the wave
+// of window w, which has X in a register, answers that one question: row w + 1 of the entry arena holds
+// {answer, X} in its first two SnapEnts (the rest of the row is never touched). No bitmap of window w + 1 is
+// needed: its own chain is by definition the chain from W1, so two pointers p = X and q = W1, the one behind
+// stepping one token at a time, meet at the first position of chain(X) that lies on chain(W1).
+// The walk reads staged bytes only: the index stage reaches IDX_EXT bytes past the window end.
+#ifndef PF_IDX_EXT   // (probe builds measure merge distances past the product's values with other ones)
+#define PF_IDX_EXT 512
+#endif
+#ifndef PF_IDX_STEPS
+#define PF_IDX_STEPS 384
+#endif
+constexpr uint32_t IDX_EXT = PF_IDX_EXT;
+constexpr uint32_t IDX_STAGE = SNAP_WIN + IDX_EXT + 32;   // + alignment shift (< 16) + a token read's dword pair
+constexpr uint32_t IDX_LDS = IDX_STAGE + SNAP_WWORDS * 4 + 64 * 4;   // k_snappy_index's static LDS
+static_assert(IDX_EXT % 16 == 0 && IDX_EXT >= 64, "whole 16-byte chunks; seq_parse looks 64 positions ahead");
+static_assert(IDX_EXT > 512 || IDX_LDS <= 10240, "k_snappy_index: 16 waves a CU need <= 10 KiB of LDS each");
+constexpr int IDX_STEPS = PF_IDX_STEPS;   // tokens both pointers may take together; longer: ENT_SLOW (exact parse)
+constexpr int DEEP_STEPS = 24;       // HBM token walks of the chain pass; longer: exact parse of the window
 constexpr uint32_t ENT_POS = 0x3fffffffu;
 enum : uint32_t { ENT_MERGE = 0, ENT_NOMERGE = 1, ENT_SLOW = 2, ENT_BAD = 3 };
+constexpr uint32_t REC_NONE = SNAP_INVALID;   // record key that answers no entry (the chain pass walks in HBM)
 
 __device__ __forceinline__ SnapEnt mk_ent(uint32_t pos, uint32_t flag, uint32_t out) {
     return SnapEnt{pos | (flag << 30), out};
 }
 
 // MERGE: pos = meeting point m, out = (true chain output in [e, m)) - (window chain output in
-// [W0, m)). NOMERGE: the chain from e leaves the window first: pos = its exit, out = its output.
-// SLOW: not resolved within ENT_STEPS tokens. BAD: the chain from e runs past the stream end.
-// Linear stage; sb = the window chain's token-start bits, pre[r] = its output before lane region r.
-__device__ SnapEnt ent_walk(uint32_t e, uint32_t W0, uint64_t wend, uint64_t n, const uint8_t* stage, uint32_t woff,
-                            const uint32_t* sb, const uint32_t* pre) {
-    uint64_t q = e;
-    uint32_t acc = 0;
-    int steps = 0;
-    for (;;) {
-        if (q >= wend) return mk_ent(uint32_t(q), ENT_NOMERGE, acc);
-        const uint32_t r = uint32_t(q) - W0;
-        if ((sb[r >> 5] >> (r & 31u)) & 1u) break;
-        if (steps == ENT_STEPS) return mk_ent(e, ENT_SLOW, 0);
-        uint32_t ol;
-        const uint64_t tl = stage_tok(stage, woff + r, ol);
-        acc += ol;
-        q += tl;
-        steps++;
-        if (q > n) return mk_ent(e, ENT_BAD, 0);
-    }
-    const uint32_t rel = uint32_t(q) - W0, rq = rel / SNAP_RB;
-    uint32_t g = pre[rq];
-    for (uint32_t b = rq * SNAP_RB; b < rel; b += 32) {
-        const uint32_t hi = rel - b >= 32 ? 0xffffffffu : ((1u << (rel - b)) - 1u);
-        uint32_t mm = sb[b >> 5] & hi;
-        while (mm) {
-            const uint32_t i = b + uint32_t(__ffs(mm) - 1);
-            mm &= mm - 1;
-            uint32_t ol;
-            stage_tok(stage, woff + i, ol);
-            g += ol;
+// [W1, m)), wrapping. NOMERGE (deep_walk only): the chain from e leaves the window first: pos = its exit,
+// out = its output. SLOW: not resolved within the step cap. BAD: the chain from e runs past the stream end.
+//
+// Two-pointer walk for the entry X of the window at W1 (W1 <= X < wend1 = the window's end, X - W1 < IDX_EXT),
+// uniform over the wave: every operand is wave-uniform and the token word goes through readfirstlane, so the
+// lengths are computed on the scalar unit. key = X when `return` answers X; REC_NONE when the walk would need
+// a byte at or past W1 + IDX_EXT or the stream end, or the chains meet outside the window (not classified
+// here: deep_walk tells NOMERGE from BAD). A walk that runs out of staged bytes after the chain from X took
+// DEEP_STEPS tokens answers SLOW like one that runs out of steps: deep_walk would give up on it too.
+__device__ SnapEnt succ_walk(const uint8_t* stage, uint32_t base, uint32_t X, uint32_t W1, uint32_t wend1, uint32_t n32,
+                             uint32_t& key, uint32_t& steps, uint32_t& need) {
+    const uint32_t lim = min(W1 + IDX_EXT, n32);
+    uint32_t p = X, q = W1, ap = 0, aq = 0, kp = 0;
+    key = REC_NONE;
+    need = 0;
+    for (steps = 0;; steps++) {
+        if (p == q) {
+            if (p >= wend1) break;
+            key = X;
+            return mk_ent(p, ENT_MERGE, ap - aq);
         }
+        const bool pb = p < q;
+        const uint32_t lo = pb ? p : q;
+        if (lo >= lim) {
+            if (kp >= uint32_t(DEEP_STEPS)) key = X;
+            break;
+        }
+        if (steps == uint32_t(IDX_STEPS)) {
+            key = X;
+            break;
+        }
+        const uint32_t a = base + lo;
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(stage + (a & ~3u));
+        const uint32_t w0 = __builtin_amdgcn_readfirstlane(w[0]), w1 = __builtin_amdgcn_readfirstlane(w[1]);
+        uint32_t ol, tl;
+        tok_lens(uint32_t(((uint64_t(w1) << 32) | w0) >> (8u * (a & 3u))), ol, tl);
+        need = lo + 4u - W1;
+        const uint32_t np = __builtin_elementwise_add_sat(lo, tl);
+        if (np > n32) break;   // past the stream end
+        if (pb) { p = np; ap += ol; kp++; } else { q = np; aq += ol; }
     }
-    return mk_ent(uint32_t(q), ENT_MERGE, acc - g);
+    return mk_ent(X, ENT_SLOW, 0);
 }
 
 __device__ __forceinline__ uint32_t wave_sum_sat(uint32_t v) {
@@ -541,7 +573,7 @@ __device__ __forceinline__ void store_window(uint32_t* tm, uint32_t* lo, const W
 __global__ __launch_bounds__(64) void k_snappy_index(const SnappyJob* __restrict__ jobs, const int2* __restrict__ wins,
                                                      SnapWin* __restrict__ win, SnapEnt* __restrict__ ent,
                                                      uint32_t* __restrict__ lane_out, int* __restrict__ fb) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SNAP_WSTAGE];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[IDX_STAGE];
     __shared__ __attribute__((aligned(16))) uint32_t sbits[SNAP_WWORDS];
     __shared__ uint32_t slo[64];
     const int2 jw = wins[blockIdx.x];
@@ -572,16 +604,30 @@ __global__ __launch_bounds__(64) void k_snappy_index(const SnappyJob* __restrict
     const uint64_t wend = min(uint64_t(W0) + SNAP_WIN, n);
 #ifdef PF_STAMPS
     unsigned long long it0 = __builtin_amdgcn_s_memtime();
+    const unsigned long long itw = it0;
 #endif
-    const uint32_t woff = snap_stage(stage, job.src, n, W0, SNAP_WSTAGE, lane);
+    const uint32_t woff = snap_stage(stage, job.src, n, W0, IDX_STAGE, lane);
     __syncthreads();
     uint32_t flags;
     uint32_t X = win_parse_spec(stage, woff, W0, n, entry, L, flags, sbits);
 #ifdef PF_STAMPS
-    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) { CSTAMP(0, 1); CSTAMP(1, t_ - it0); if (flags & WIN_NOCONV) CSTAMP(2, 1); } it0 = t_; }
+    // The phase times are kept in registers and added to the table at the wave's end, so that no phase holds
+    // lane 0's atomics of the one before (3400 waves add to the same addresses). The spans are wave residency,
+    // not work: DESIGN 4.37.
+    unsigned long long st_spec, st_sum, st_store;
+    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_spec = t_ - it0; it0 = t_; }
+#define IDX_FLUSH(t_end)                                                                               \
+    do {                                                                                               \
+        if (lane == 0) {                                                                               \
+            CSTAMP(0, 1); CSTAMP(1, st_spec); CSTAMP(26, st_sum); CSTAMP(3, st_store);                 \
+            CSTAMP(25, (t_end) - itw);                                                                 \
+            if (noconv) CSTAMP(2, 1);                                                                  \
+        }                                                                                              \
+    } while (0)
 #endif
     uint32_t sum;
-    if (flags & WIN_NOCONV) {   // chains that do not synchronise: exact whole-wave parse instead
+    const bool noconv = flags & WIN_NOCONV;
+    if (noconv) {   // chains that do not synchronise: exact whole-wave parse instead
         reinterpret_cast<uint4*>(sbits)[lane] = make_uint4(0, 0, 0, 0);
         slo[lane] = 0;
         __syncthreads();
@@ -594,36 +640,46 @@ __global__ __launch_bounds__(64) void k_snappy_index(const SnappyJob* __restrict
     } else {
         sum = wave_sum_sat(L.out);
     }
+#ifdef PF_STAMPS   // (the wave sum apart from the stores)
+    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_sum = t_ - it0; }
+#endif
     store_window(tm, lo, L, lane);
     if (lane == 0) win[wi] = SnapWin{entry, X, sum, flags};
 #ifdef PF_STAMPS
-    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) CSTAMP(3, t_ - it0); it0 = t_; }
+    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_store = t_ - it0; it0 = t_; }
 #endif
-    if (jw.y == 0) return;   // window 0's entry is exact: no table
-    // entry table: lane d follows the chain from W0 + d until it meets this window's chain
-    __syncthreads();
-    reinterpret_cast<uint4*>(sbits)[lane] = make_uint4(L.b0, L.b1, L.b2, L.b3);
-    {   // exclusive prefix of the lane-region outputs (wrapping: only differences are used)
-        uint32_t x = L.out;
-        #pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t y = __shfl_up(x, dd, 64);
-            if (lane >= dd) x += y;
-        }
-        slo[lane] = x - L.out;
-    }
-    __syncthreads();
-    SnapEnt T = mk_ent(0, ENT_SLOW, 0);
-    if (!(flags & WIN_BROKEN) && uint64_t(W0) + lane < wend)
-        T = ent_walk(W0 + uint32_t(lane), W0, wend, n, stage, woff, sbits, slo);
-    ent[size_t(wi) * 64 + lane] = T;
+    if (uint32_t(jw.y) + 1 >= job.n_win) {   // the page's last window: no successor
 #ifdef PF_STAMPS
-    {
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-        if (lane == 0) CSTAMP(4, t_ - it0);
-        const unsigned long long sl = __ballot((T.pos >> 30) == ENT_SLOW);
-        if (lane == 0 && sl) CSTAMP(5, 1);
-        if (lane == 0) CSTAMP(6, __popcll(sl));
+        IDX_FLUSH(it0);
+#endif
+        return;
+    }
+    // successor record: the answer for window w + 1's entry X, or none (window broken or parsed exactly, the
+    // chain jumps over window w + 1 (WM_SKIP in the chain pass), or X lies past the staged extension)
+    const uint32_t W1 = W0 + SNAP_WIN;
+    const uint32_t wend1 = uint32_t(min(uint64_t(W1) + SNAP_WIN, n));
+    X = __builtin_amdgcn_readfirstlane(X);
+    SnapEnt R = mk_ent(0, ENT_SLOW, 0);
+    uint32_t key = REC_NONE, steps = 0, need = 0;
+    const bool asked = !noconv && !(flags & WIN_BROKEN) && X != SNAP_INVALID && X < wend1;
+    if (asked && X - W1 < IDX_EXT) R = succ_walk(stage, woff - W0, X, W1, wend1, uint32_t(n), key, steps, need);
+    if (lane == 0) *reinterpret_cast<uint4*>(ent + size_t(wi + 1) * 64) = make_uint4(R.pos, R.out, key, 0u);
+#ifdef PF_STAMPS
+    const unsigned long long t_ = __builtin_amdgcn_s_memtime();
+    IDX_FLUSH(t_);
+#undef IDX_FLUSH
+    if (lane == 0) {
+        CSTAMP(9, t_ - it0);
+        CSTAMP(4, steps);
+        if (asked) CSTAMP(15, 1);
+        if (asked && key == REC_NONE) CSTAMP(10, 1);
+        if (key != REC_NONE && (R.pos >> 30) == ENT_SLOW) CSTAMP(5, 1);
+        if (key != REC_NONE && (R.pos >> 30) == ENT_MERGE) {   // histogram of the bytes a resolved walk needed
+            CSTAMP(6, need);
+            uint32_t b = 0;
+            while (b < 7 && need > (32u << b)) b++;
+            CSTAMP(32 + b, 1);
+        }
     }
 #endif
 }
@@ -634,11 +690,10 @@ constexpr int FIX_MAXW = 1024;       // pages up to 8 MiB compressed (larger: se
 
 __device__ __forceinline__ bool tm_get(const uint32_t* tm, uint32_t i) { return (tm[i >> 5] >> (i & 31u)) & 1u; }
 
-constexpr int DEEP_STEPS = 24;       // HBM token walks of the chain pass; longer: exact parse of the window
-
-// Entry deeper than 64 bytes into window w (after a long literal): follow the chain from e in HBM
-// until it meets the window's own chain (bitmap) or leaves the window. The window chain's output in
-// [W0, m) is the lane-region counts before m's region plus the tokens of m's region below m.
+// An entry of window w that its record does not answer (deeper than IDX_EXT bytes, after a long
+// literal; or not the predecessor's own exit): follow the chain from e in HBM until it meets the
+// window's own chain (bitmap) or leaves the window. The window chain's output in [W0, m) is the
+// lane-region counts before m's region plus the tokens of m's region below m.
 __device__ SnapEnt deep_walk(const SnappyJob& job, uint32_t w, uint32_t e, uint64_t wend, const uint32_t* LOw) {
     const uint64_t n = job.src_len;
     const uint32_t W0 = w * SNAP_WIN;
@@ -674,12 +729,13 @@ __device__ SnapEnt deep_walk(const SnappyJob& job, uint32_t w, uint32_t e, uint6
 // One wave per page, lanes over windows. Window 0's entry is exact (after the varint); window w's
 // true entry is window w-1's true exit. Every window's exit as a function of its entry is known
 // from the index pass for entries that merge with the window's own chain (exit = the window's own
-// exit) or that leave it first (the entry table); so all windows are evaluated at once from a
-// guessed entry (the previous window's own exit) and re-evaluated where the previous exit
-// changed, until the entries are consistent: the fixed point of e_w = exit_{w-1}(e_{w-1}) with
-// e_1 exact is unique, so a consistent assignment is the true chain. Usually two rounds, each one
-// table load per window. A window the table cannot resolve (entry not within ENT_STEPS tokens of
-// the chain) stops the propagation; the first such window is parsed exactly by the whole wave
+// exit) or that leave it first (deep_walk); so all windows are evaluated at once from a
+// guessed entry (the previous window's own exit, which the successor record answers) and
+// re-evaluated where the previous exit changed, until the entries are consistent: the fixed point
+// of e_w = exit_{w-1}(e_{w-1}) with e_1 exact is unique, so a consistent assignment is the true
+// chain. Usually two rounds, each one record load per window. A window neither the record nor the
+// walk resolves (entry not within IDX_STEPS / DEEP_STEPS tokens of the chain) stops the
+// propagation; the first such window is parsed exactly by the whole wave
 // once its entry is final, and the rounds continue behind it. The result replaces each window's
 // SnapWin: {true entry, merge point / exit, true output bytes, WM_* mode}.
 // LDS: the DP stage of the exact window parse (25 KiB) plus five per-window words sized by the host
@@ -745,14 +801,19 @@ __global__ __launch_bounds__(64) void k_snappy_chain(const SnappyJob* __restrict
                 } else {
                     const SnapWin sw = Wn[w];
                     SnapEnt T = mk_ent(e, ENT_SLOW, 0);
-                    const uint32_t d = e - W0;
                     if (!(sw.flags & WIN_BROKEN)) {
 #ifdef PF_STAMPS
                         const unsigned long long dt0 = __builtin_amdgcn_s_memtime();
 #endif
-                        T = d < 64 ? E[size_t(w) * 64 + d] : deep_walk(job, w, e, wend, LO + size_t(w) * 64);
+                        // the record window w - 1 left, if it answers this entry; else a walk in HBM. A record
+                        // that did not resolve its own entry stands for every entry: where the chains from W0 and
+                        // from one entry stay apart that long, they do from the others (in SF1, 3984 of the 4032
+                        // entries of such windows; round 6), and the walk would cost a third of the exact parse.
+                        const uint4 rec = *reinterpret_cast<const uint4*>(E + size_t(w) * 64);
+                        const bool hit = rec.z == e || (rec.z != REC_NONE && (rec.x >> 30) == ENT_SLOW);
+                        T = hit ? SnapEnt{rec.x, rec.y} : deep_walk(job, w, e, wend, LO + size_t(w) * 64);
 #ifdef PF_STAMPS
-                        if (d >= 64) { CSTAMP(11, 1); CSTAMP(12, __builtin_amdgcn_s_memtime() - dt0); }
+                        if (!hit) { CSTAMP(11, 1); CSTAMP(12, __builtin_amdgcn_s_memtime() - dt0); }
 #endif
                     }
                     const uint32_t fl = T.pos >> 30, tp = T.pos & ENT_POS;
