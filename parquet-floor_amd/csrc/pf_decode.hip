@@ -9,7 +9,7 @@
 //   K5 DELTA_BINARY_PACKED (DeltaBinaryPackingValuesReader[ForLong]) — pf_delta.hip
 //   K6 null scatter: def == maxDef test of ParquetReader.java:146 -> validity + slot positions
 //   K7 repetition levels -> list offsets (ParquetReader.java:200's rep stream)
-// Flat columns take the faster kernels of pf_pages.hip where those apply, PLAIN BYTE_ARRAY length
+// Flat columns take the faster kernels of the pf_flat*.hip units where those apply, PLAIN BYTE_ARRAY length
 // chains are walked by pf_ba.hip; every page they leave is decoded here.
 //
 // Kernels (256 threads, entries in tiles of TILE, unless noted):
@@ -1061,7 +1061,7 @@ void launch_nest_decode(const DevChunk* d_chunks, DevPage* d_pages, const int2* 
 }
 void launch_count(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, BaJob* d_bajobs,
                   hipStream_t st, int idle_grid) {
-    // d_list: every page that needs counts; the ones launch_count_flat (pf_pages.hip, before this on the
+    // d_list: every page that needs counts; the ones launch_count_flat (pf_flat_count.hip, before this on the
     // stream) counted are skipped by their pg.counted mark
     if (n > 0) hipLaunchKernelGGL(k_count, dim3(std::min(n, idle_grid)), dim3(NT), 0, st, d_chunks, d_pages, d_list, n, d_res, d_bajobs);
 }

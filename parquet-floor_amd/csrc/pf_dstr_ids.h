@@ -1,7 +1,7 @@
 // pf_dstr_ids.h — the dictionary ids of 16 consecutive values from a page's id run table, one text for the kernel
-// (k_flat_dstr, pf_pages.hip) and for the host check (tests/native/pf_dstr_ids_check.cpp), shared like pf_pred.h.
+// (k_flat_dstr, pf_flat_dstr.hip) and for the host check (tests/native/pf_dstr_ids_check.cpp), shared like pf_pred.h.
 //
-// The run table is k_runs' (pf_pages.hip): row i = {first value | packed << 31, RLE value or the bit offset of the
+// The run table is k_runs' (pf_flat_count.hip): row i = {first value | packed << 31, RLE value or the bit offset of the
 // run's packed values in the id stream}; a run ends where the next one starts, the last one at `cov`.
 // The id stream is read through a word loader W: W(w) is the little-endian 32-bit word w of a frame in which stream
 // bit b is frame bit b + bias (the kernel's frame is its LDS stage, which starts at a 16-byte aligned address at

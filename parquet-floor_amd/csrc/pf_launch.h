@@ -39,12 +39,22 @@ void launch_snappy_litcopy(const SnappyJob* d_jobs, const int* d_list, int n, co
 void launch_ba(BaJob* d_jobs, int n_jobs, const int2* d_tiles, int n_tiles, DevChunkResult* d_res, hipStream_t st,
                bool short_values);
 
-// pf_pages.hip
+// pf_flat_count.hip
 void launch_runs(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st);
-void launch_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st,
-                bool page_null, NullCaps nc);
 void launch_count_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, int n_flat, const int2* d_dblk,
                        int n_dblk, DevChunkResult* d_res, BaJob* d_bajobs, hipStream_t st);
+
+// pf_flat_null.hip (launch_flat_null: called by launch_flat, first in the flat stage)
+void launch_lvl(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int n, DevChunkResult* d_res, hipStream_t st,
+                bool page_null, NullCaps nc);
+void launch_flat_null(const DevChunk* d_chunks, DevPage* d_pages, const int2* blocks, int n4, int n8, int* d_fbq,
+                      DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
+
+// pf_flat_dstr.hip (called by launch_flat, between k_flat_fixed and k_flat_all)
+void launch_flat_dstr(const DevChunk* d_chunks, DevPage* d_pages, const int2* d_dblk, int n_dblk, DevChunkResult* d_res,
+                      hipStream_t st);
+
+// pf_flat.hip: the flat stage (what the runtime calls)
 void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
                  const int2* d_dblk, int n_dblk, DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);
 

@@ -1,5 +1,5 @@
-// pf_pages.h — device code shared by the page-decode units (pf_ba.hip, pf_pages.hip, pf_decode.hip,
-// pf_snappy_head.hip). The build has no relocatable device code, so every function here is
+// pf_pages.h — device code shared by the page-decode units (pf_ba.hip, the pf_flat*.hip units
+// through pf_flat.h, pf_decode.hip, pf_snappy_head.hip). The build has no relocatable device code, so every function here is
 // compiled again in each unit that calls it; nothing in this header defines a kernel or a
 // __device__ variable.
 //

@@ -1,4 +1,4 @@
-"""k_flat_dstr (pf_pages.hip): flat dictionary BYTE_ARRAY pages with a small dictionary of short values, decoded one
+"""k_flat_dstr (pf_flat_dstr.hip): flat dictionary BYTE_ARRAY pages with a small dictionary of short values, decoded one
 FBLK block per workgroup with 16 consecutive entries per thread.
 
 Every case is a file of one or more chunks assembled by tests/pagekit.py (run layouts, id widths, page layouts chosen

@@ -1,5 +1,5 @@
 """Wave-parallel run discovery (wave_run_round / wave_walk_runs, pf_pages.h) against the
-one-lane header walk it replaced (walk_runs), on random RLE / bit-packed hybrid streams: long
+one-lane header walk it replaced (walk_runs, pf_flat_count.hip), on random RLE / bit-packed hybrid streams: long
 stretches of equal bit-packed runs (what Arrow and parquet-mr write: 512 values per run), mixed
 RLE runs, empty runs, a truncated final run, streams that end early, corrupt headers, value
 windows (lo > 0), a start state past the first runs, and run tables that fill up (cap).

@@ -417,7 +417,7 @@ def _page_flags(decoder, f):
 
 
 def _check_paths(fid, f, flags):
-    """Which kernel took which page, from the guards in pf_pages.hip / pf_plan.cpp."""
+    """Which kernel took which page, from the guards in pf_flat.hip, pf_flat_dstr.hip, pf_flat_null.hip / pf_plan.cpp."""
     kind = f["kind"]
     fixed_by_bw, null_by_bw = {}, {}
     for cell, pf_ in zip(f["cells"], flags):

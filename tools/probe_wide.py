@@ -19,7 +19,7 @@ if not os.path.exists(path):
     pq.write_table(datagen.wide_table(1_000_000, ncols=ncols, pool=pool), path, compression="snappy",
                    row_group_size=1_000_000)
 L = _native.lib()
-f = L.pf_debug_pstamps
+f = L.pf_debug_nstamps   # the nullable path's own table (pf_flat_null.hip); pf_debug_pstamps is the flat kernels'
 f.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
 buf = (C.c_ulonglong * 16)()
 for cols in ([0], [ncols - 1], list(range(ncols))):
