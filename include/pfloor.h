@@ -258,6 +258,52 @@ int pf_selection_info_get(pf_ctx* ctx, pf_selection_info* out);
 /* The selected row numbers into a host buffer, synchronous; PF_ERR_CAPACITY (nothing copied) below 4 * rows_selected. */
 int pf_copy_selection(pf_ctx* ctx, int32_t* rows, size_t cap_bytes);
 
+/* Dictionary-preserving decode: keep[i] != 0 asks for chunk i as indices + dictionary instead of expanded values.
+ * keep == NULL is pf_decode_row_group, call for call.
+ * Eligibility is decided by the planner from the descriptors alone, never from page bytes. A chunk is kept when
+ * keep[i] != 0, max_rep == 0, physical_type != PF_BOOLEAN, it has a dictionary page and at least one data page, and
+ * every data page's encoding is PF_ENC_RLE_DICTIONARY or PF_ENC_PLAIN_DICTIONARY. Any other chunk (a writer that
+ * fell back to PLAIN part-way, a nested chunk, DELTA or PLAIN pages, ...) gets kept = 0 and is decoded as
+ * pf_decode_row_group decodes it, byte for byte; asking for it is never an error.
+ * index_width is the smallest of 1, 2 or 4 bytes that holds n_entries - 1 (n_entries <= 256: 1, <= 65536: 2, else 4):
+ * it follows the dictionary's size, not the id bit width the pages happen to use.
+ * A kept chunk after pf_wait: pf_column_info.width = index_width, d_values = num_slots indices (unsigned
+ * little-endian; a null slot holds 0), validity, num_entries, num_slots, num_values and num_rows exactly those of the
+ * expanding decode, d_offsets = d_chars = NULL and num_chars = 0. pf_copy_column copies values and validity and leaves
+ * non-NULL offsets / chars buffers untouched. The dictionary is described by pf_dict_info: its entries in file order
+ * (unused ones included), fixed width as n_entries * width bytes, BYTE_ARRAY as n_entries + 1 offsets and the chars.
+ * The invariant: values[s] = dict[index[s]] where the validity bit is set, zero bytes or a zero-length string where it
+ * is not (BYTE_ARRAY offsets and chars rebuilt in slot order) is bit for bit what pf_decode_row_group gives.
+ * Errors: an id >= n_entries in a present value (in a bit-packed run or as an RLE run's value) gives the chunk the
+ * status and error page the expanding decode gives it, other chunks are unaffected; a damaged dictionary page is
+ * reported as ever. An all-null chunk with an empty dictionary is valid: index_width 1, indices 0.
+ * Indices and dictionary arrays live in the batch's out and chars arenas, so pf_batch_bytes, pf_copy_batch_async and
+ * pf_column_info_host work after such a decode (the batch is that much smaller); pf_dict_info_host rebases as
+ * pf_column_info_host does. The dictionary chars count towards the chars arena's need (an overflow reruns the batch).
+ * pf_decode_row_group_rows and _filter take no keep flags: windows or predicates over kept chunks are not done. */
+int pf_decode_row_group_dict(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const uint8_t* keep,
+                             const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
+typedef struct pf_dict_info {
+    int32_t kept;          /* 1: the chunk's `values` are indices into the dictionary below; 0: decoded as always */
+    int32_t index_width;   /* 1, 2 or 4 bytes, unsigned little-endian; 0 when kept == 0 */
+    int64_t n_entries;     /* DictionaryPageHeader.num_values, in file order, unused entries included */
+    int32_t width;         /* bytes per entry (INT96 12, FLBA type_length); 0 for BYTE_ARRAY */
+    int32_t pad;
+    int64_t num_chars;     /* BYTE_ARRAY: bytes of all entries */
+    const void*    d_values;   /* n_entries * width */
+    const int32_t* d_offsets;  /* n_entries + 1, offsets[0] = 0 */
+    const uint8_t* d_chars;
+} pf_dict_info;
+/* After pf_wait: chunk i's dictionary (all zero with kept = 0 for a chunk that was not kept, also after a decode
+ * without keep flags). */
+int pf_dict_info_get(pf_ctx* ctx, int chunk, pf_dict_info* out);
+/* After pf_copy_batch_async + pf_sync: the same with the pointers rebased into the host copy. */
+int pf_dict_info_host(pf_ctx* ctx, int chunk, const void* host, pf_dict_info* out);
+/* The dictionary of a kept chunk into out->values (fixed width) or out->offsets / out->chars (BYTE_ARRAY); the other
+ * fields of `out` are ignored. Host buffers, synchronous. PF_ERR_CAPACITY (nothing copied) if a non-NULL buffer is too
+ * small; PF_ERR_STATE on a chunk with kept == 0; the chunk's own status if it failed to decode. */
+int pf_copy_dictionary(pf_ctx* ctx, int chunk, const pf_column_out* out);
+
 /* Block until the enqueued decode has finished; returns the first per-chunk error. */
 int pf_wait(pf_ctx* ctx);
 

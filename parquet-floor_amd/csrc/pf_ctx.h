@@ -110,6 +110,11 @@ struct pf_ctx {
     const pf::SnapWin* d_last_win = nullptr;
     const uint32_t* d_last_lane_out = nullptr;
     std::vector<pf_column_info> info;
+    // kept dictionaries (pf_decode_row_group_dict): the call's flags (empty: none), every chunk's pf_dict_info after
+    // pf_wait, and the pinned mirror the DevKeep table comes down into
+    std::vector<uint8_t> keep_flags;
+    std::vector<pf_dict_info> dinfo;
+    pf::HostBuf h_keep;
     bool meta_by_kernel = false;   // this batch's metadata went up by k_upload (which also zeroes bits / npub)
     uint64_t chars_need = 0;
     int reruns = 0;

@@ -302,6 +302,22 @@ struct DevChunkResult {
     int32_t err_page;
 };
 
+// Kept dictionaries (pf_flat_ids.hip, pf_decode_row_group_dict): one DevKeep per chunk that is decoded to indices +
+// dictionary. The chunk's DevChunk.values holds its indices (index_width bytes per slot); it has no offsets or chars of
+// its own and is on none of the count, scan, flat or decode lists. The dictionary's output arrays lie in the out arena
+// (values, or offsets) and, for BYTE_ARRAY, in the chars arena (k_dict_offsets takes the room and writes d_chars /
+// num_chars, which come down with the results).
+struct DevKeep {
+    int32_t chunk;
+    int32_t index_width;      // 1, 2 or 4
+    int64_t n_entries;
+    uint8_t* d_values;        // fixed width: n_entries * width bytes
+    int32_t* d_offsets;       // BYTE_ARRAY: n_entries + 1
+    uint8_t* d_chars;         // BYTE_ARRAY: device-written (null: the arena was full)
+    int64_t num_chars;        // device-written
+};
+constexpr uint32_t DICT_LONG = 64;           // k_dict_pack: entries longer than this are copied by the whole workgroup
+
 // Row windows (pf_window.hip, pf_decode_row_group_rows): one DevWin per chunk whose window is not {0, -1}, and what
 // k_win_bounds finds for it. k_win_copy writes the window's arrays into the twin output arenas (out, bits, chars: the
 // decode arenas' sizes and per-chunk offsets), in tiles of WIN_TILE output bytes per array.

@@ -54,6 +54,11 @@ void launch_flat_null(const DevChunk* d_chunks, DevPage* d_pages, const int2* bl
 void launch_flat_dstr(const DevChunk* d_chunks, DevPage* d_pages, const int2* d_dblk, int n_dblk, DevChunkResult* d_res,
                       hipStream_t st);
 
+// pf_flat_ids.hip: kept-dictionary chunks (pf_decode_row_group_dict), at the end of the flat stage
+void launch_flat_ids(const DevChunk* d_chunks, DevPage* d_pages, const int2* d_blocks, int n_blocks, DevKeep* d_keeps, int n_keeps,
+                     const int* d_keep_of, DevChunkResult* d_res, uint8_t* chars_arena, uint64_t arena_cap,
+                     unsigned long long* arena_used, hipStream_t st);
+
 // pf_flat.hip: the flat stage (what the runtime calls)
 void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, int nfix, int n, int n4, int n8, int* d_fbq,
                  const int2* d_dblk, int n_dblk, DevChunkResult* d_res, hipStream_t st, NullCaps nc, int stagger);

@@ -15,6 +15,19 @@ bool dict_encoded(int e) { return e == PF_ENC_PLAIN_DICTIONARY || e == PF_ENC_RL
 bool int_type(int t) { return t == PF_INT32 || t == PF_INT64; }
 }  // namespace
 
+bool keep_eligible(const pf_chunk_desc& cd) {
+    if (cd.max_rep != 0 || cd.physical_type == PF_BOOLEAN || cd.n_pages <= 0 || !cd.pages) return false;
+    int n_dict = 0, n_data = 0;
+    for (int i = 0; i < cd.n_pages; i++) {
+        const pf_page_desc& pd = cd.pages[i];
+        if (pd.page_type == PF_PAGE_DICTIONARY) { n_dict++; continue; }
+        if (pd.page_type != PF_PAGE_DATA && pd.page_type != PF_PAGE_DATA_V2) continue;   // index pages
+        if (!dict_encoded(pd.encoding)) return false;
+        n_data++;
+    }
+    return n_dict > 0 && n_data > 0;
+}
+
 int type_width(int ptype, int type_length) {
     switch (ptype) {
     case PF_BOOLEAN: return 1;
@@ -88,7 +101,8 @@ namespace {
 
 // The chunk's DevChunk, its pages, their scratch regions and Snappy jobs, its output arrays.
 // A chunk that fails validation keeps its status and loses its pages and jobs.
-void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& opts, BatchPlan& p, uint64_t& nest_pub) {
+void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& opts, BatchPlan& p, uint64_t& nest_pub,
+                bool want_keep) {
     // nested pages: entries per segment (k_nest_*); PF_NEST_SEG=n (tests) sets it and sends every
     // eligible nested page, one segment or more, down the segment path (0: none)
     int64_t nest_seg_len = NEST_SEG;
@@ -113,7 +127,10 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
     else if (cd.max_def < 0 || cd.max_def > 255 || cd.max_rep < 0 || cd.max_rep > 255 || cd.n_pages < 0 ||
              (cd.n_pages > 0 && !cd.pages) || cd.chunk_offset + cd.chunk_size > n_bytes)
         hs = PF_ERR_INVALID_ARG;
-    ck.needs_count = (cd.physical_type == PF_BYTE_ARRAY || cd.max_rep > 0) ? 1 : 0;
+    // kept dictionary: indices + dictionary instead of values (the rule reads the descriptors only; a chunk that
+    // fails validation fails as ever)
+    const bool kept = want_keep && hs == 0 && keep_eligible(cd);
+    ck.needs_count = (!kept && (cd.physical_type == PF_BYTE_ARRAY || cd.max_rep > 0)) ? 1 : 0;
     int64_t entries = 0;
     int dict_global = -1;
     size_t& scratch = p.scratch_bytes;
@@ -180,7 +197,9 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                 ck.n_pages++;
                 // FIXED_LEN_BYTE_ARRAY in DELTA_BYTE_ARRAY (parquet-mr's v2 writer after a dictionary fallback)
                 const bool flba_dba = cd.physical_type == PF_FIXED_LEN_BYTE_ARRAY && pd.encoding == PF_ENC_DELTA_BYTE_ARRAY;
-                if (cd.physical_type == PF_BYTE_ARRAY)   // value positions / ids + per-block chars (k_flat)
+                if (kept) {
+                    // (k_flat_ids reads the id stream through k_runs' table: no value positions, no chars)
+                } else if (cd.physical_type == PF_BYTE_ARRAY)   // value positions / ids + per-block chars (k_flat)
                     pp.aux_off = take(scratch, aux_chars_bytes(uint64_t(pd.num_values)), 256);
                 else if (flba_dba)   // slot of every present value (decode_page -> k_dba_chars)
                     pp.aux_off = take(scratch, 4ull * pd.num_values + 16, 256);
@@ -196,14 +215,14 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
                     }
                 }
                 if (pp.aux_off != NO_OFF) pg.aux_cap = pg.num_values;
-                if (cd.physical_type == PF_BYTE_ARRAY) p.chars_hint += pd.uncompressed_size;
+                if (cd.physical_type == PF_BYTE_ARRAY && !kept) p.chars_hint += pd.uncompressed_size;
                 if (flba_dba || (cd.physical_type == PF_BYTE_ARRAY &&
                                  (pd.encoding == PF_ENC_DELTA_LENGTH_BYTE_ARRAY || pd.encoding == PF_ENC_DELTA_BYTE_ARRAY)))
                     pp.dx_off = take(scratch, dx_bytes(uint64_t(pd.num_values)), 256);   // k_dlen
                 if (cd.max_rep == 0 && cd.physical_type != PF_BOOLEAN && dict_encoded(pd.encoding))
                     pp.rt_off = take(scratch, RT_BYTES, 256);   // k_runs table
-                if (cd.max_rep == 0 && cd.max_def > 0 && cd.physical_type != PF_BOOLEAN && cd.physical_type != PF_BYTE_ARRAY &&
-                    pd.num_nulls != 0 &&   // v2 header / v1 page statistics say when no level is null (-1: unknown)
+                if (cd.max_rep == 0 && cd.max_def > 0 && cd.physical_type != PF_BOOLEAN &&
+                    (cd.physical_type != PF_BYTE_ARRAY || kept) && pd.num_nulls != 0 &&   // v2 header / v1 page statistics say when no level is null (-1: unknown)
                     (pd.encoding == PF_ENC_PLAIN || dict_encoded(pd.encoding))) {
                     pp.lt_off = take(scratch, lvl_table_bytes(pg.num_values), 256);   // k_lvl tables
                     pg.lvl_cap = lvl_table_cap(pg.num_values);
@@ -244,7 +263,19 @@ void plan_chunk(const pf_chunk_desc& cd, int c, size_t n_bytes, const PfOpts& op
     ck.num_entries = entries;
     OutPlan& op = p.oplan[size_t(c)];
     op = OutPlan{NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF, NO_OFF};
-    if (hs == 0) {
+    if (hs == 0 && kept) {   // indices, validity, and the dictionary's own arrays
+        size_t &out = p.out_bytes, &bits = p.bits_bytes;
+        KeepPlan kp{c, dict_index_width(ck.dict_n), ck.dict_n, ck.width, NO_OFF, NO_OFF};
+        op.values = take(out, size_t(entries) * size_t(kp.index_width));
+        if (cd.max_def > 0) op.validity = take(bits, align_up((entries + 7) / 8, 4), 256);
+        if (ck.width > 0) kp.values = take(out, size_t(kp.n_entries) * size_t(ck.width));
+        else {
+            kp.offsets = take(out, 4 * size_t(kp.n_entries + 1));
+            p.chars_hint += p.pages[size_t(ck.dict_page)].body_len;   // (the dictionary's chars are in the chars arena)
+        }
+        p.keep_of[size_t(c)] = int32_t(p.keeps.size());
+        p.keeps.push_back(kp);
+    } else if (hs == 0) {
         size_t &out = p.out_bytes, &bits = p.bits_bytes;
         if (ck.width > 0) op.values = take(out, size_t(entries) * ck.width);
         if (cd.max_def > 0) op.validity = take(bits, align_up((entries + 7) / 8, 4), 256);
@@ -300,7 +331,7 @@ void plan_page_tables(BatchPlan& p) {
             p.lists[L_LVL].push_back(int(i));
             const DevChunk& lc = p.chunks[size_t(pg.chunk)];
             const uint64_t db = uint64_t(std::max<int64_t>(lc.dict_n, 0)) * uint64_t(std::max(lc.width, 0));
-            if (lc.dict_page >= 0 && db > 0 && db <= NULL_DICT_LDS)
+            if (lc.dict_page >= 0 && db > 0 && db <= NULL_DICT_LDS && p.keep_of[size_t(pg.chunk)] < 0)
                 p.null_caps.dlds = std::max(p.null_caps.dlds, uint32_t(align_up(db, 256)));
             // level / id byte stages: FBLK values of the level width / the dictionary's id width
             // (bit width of its largest index, as writers choose it) + run headers
@@ -352,6 +383,11 @@ void plan_routes(const PfOpts& opts, BatchPlan& p) {
         const PagePlan& pp = p.pplan[i];
         if (pg.flags & PG_DICT) continue;
         const DevChunk& ck = p.chunks[size_t(pg.chunk)];
+        if (p.keep_of[size_t(pg.chunk)] >= 0) {   // a kept chunk's pages reach k_flat_ids and nothing that expands them
+            const int nb = std::max(1, int((int64_t(pg.num_values) + FBLK - 1) / FBLK));
+            for (int b = 0; b < nb; b++) { p.lists[L_IDS].push_back(int(i)); p.lists[L_IDS].push_back(b); }
+            continue;
+        }
         const bool has_lvltab = pp.lt_off != NO_OFF;
         if (pg.encoding == PF_ENC_DELTA_BINARY_PACKED && pp.aux_off != NO_OFF && ck.ptype != PF_BYTE_ARRAY)
             p.lists[L_DELTA].push_back(int(i));
@@ -471,18 +507,22 @@ void plan_meta(BatchPlan& p) {
     p.off_nfbq = take(m, 16 + sizeof(Int2) * size_t(p.n_flat_fixed + p.n_null4 + p.n_null8), 16);   // fallback queue
     p.off_zjobs = take(m, sizeof(ZstdJob) * p.zjobs.size());
     p.off_ljobs = take(m, sizeof(Lz4Job) * p.ljobs.size());
+    p.off_keeps = take(m, sizeof(DevKeep) * p.keeps.size());
+    p.off_keepof = take(m, p.keeps.empty() ? 0 : sizeof(int32_t) * size_t(p.n_chunks));
     p.meta_bytes = take(m, 256) + 256;   // arena counter lives in the last 256 bytes
 }
 
 }  // namespace
 
-void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const PfOpts& opts, BatchPlan& p) {
+void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const PfOpts& opts, BatchPlan& p, const uint8_t* keep) {
     p.n_chunks = n_chunks;
     p.chunks.assign(size_t(n_chunks), DevChunk{});
     p.host_status.assign(size_t(n_chunks), 0);
     p.oplan.resize(size_t(n_chunks));
     p.pages.clear(); p.pplan.clear(); p.jobs.clear(); p.zjobs.clear(); p.ljobs.clear();
     p.bajobs.clear(); p.ba_tiles.clear(); p.ba_bm.clear();
+    p.keeps.clear(); p.dkeeps.clear();
+    p.keep_of.assign(size_t(n_chunks), -1);
     for (auto& l : p.lists) l.clear();
     p.ba_short_dict = p.ba_short_data = true;
     p.max_nwin = p.max_dbp_nwin = 0;
@@ -490,7 +530,7 @@ void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const Pf
     p.scratch_bytes = p.out_bytes = p.bits_bytes = 0;
     p.chars_hint = 0;
     uint64_t nest_pub = 0;
-    for (int c = 0; c < n_chunks; c++) plan_chunk(cds[c], c, n_bytes, opts, p, nest_pub);
+    for (int c = 0; c < n_chunks; c++) plan_chunk(cds[c], c, n_bytes, opts, p, nest_pub, keep && keep[c]);
     plan_ba_walks(p);
     p.npub_bytes = size_t(nest_pub);
     p.off_npub = take(p.scratch_bytes, p.npub_bytes, 256);
@@ -576,6 +616,16 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
         ck.list_validity = at(a.bits, op.list_validity);
         ck.def_levels = at(a.out, op.def);
         ck.rep_levels = at(a.out, op.rep);
+    }
+    p.dkeeps.clear();
+    for (const KeepPlan& kp : p.keeps) {
+        DevKeep k{};
+        k.chunk = kp.chunk;
+        k.index_width = kp.index_width;
+        k.n_entries = kp.n_entries;
+        k.d_values = at(a.out, kp.values);
+        k.d_offsets = reinterpret_cast<int32_t*>(at(a.out, kp.offsets));
+        p.dkeeps.push_back(k);
     }
 }
 

@@ -3,7 +3,7 @@
 // routing of every page can be checked without a GPU (tests/native/pf_plan_check.cpp).
 //
 //   plan_batch  descriptors -> DevChunk / DevPage / SnappyJob / ZstdJob / Lz4Job / BaJob tables, the launch lists and
-//               grids, the arena sizes and the metadata layout. Offsets only.
+//               grids, the arena sizes and the metadata layout; which chunks keep their dictionary. Offsets only.
 //   bind_batch  offsets -> device pointers, given where the runtime allocated the arenas.
 #pragma once
 #include <cstddef>
@@ -38,6 +38,7 @@ enum ListId {
     L_CDICT,    // (page, block) pairs of flat dictionary BYTE_ARRAY pages (k_count_dict)
     L_ZSTD,     // ZSTD jobs in dispatch order: the most compressed bytes first (k_zstd)
     L_LZ4,      // LZ4_RAW jobs in dispatch order: the most compressed bytes first (k_lz4)
+    L_IDS,      // (page, block) pairs of the data pages of kept-dictionary chunks, FBLK entries each (k_flat_ids)
     N_LISTS
 };
 
@@ -84,6 +85,19 @@ struct ArenaBases {
     uintptr_t in, scratch, out, bits, meta, tokmap;
 };
 
+// A kept-dictionary chunk (pf_decode_row_group_dict): its index width and where its dictionary's output arrays lie
+// in the out arena (NO_OFF: it has none; the chars of a BYTE_ARRAY dictionary are placed on the device).
+struct KeepPlan {
+    int32_t chunk, index_width;
+    int64_t n_entries;
+    int32_t width;            // bytes per dictionary entry, 0 for BYTE_ARRAY
+    uint64_t values, offsets;
+};
+// 1, 2 or 4: the smallest index that holds n_entries - 1.
+inline int dict_index_width(int64_t n_entries) { return n_entries <= 256 ? 1 : (n_entries <= 65536 ? 2 : 4); }
+// The eligibility rule of pf_decode_row_group_dict (include/pfloor.h), from the descriptor alone.
+bool keep_eligible(const pf_chunk_desc& cd);
+
 // Everything one batch needs between its descriptors and its launches.
 struct BatchPlan {
     int n_chunks = 0;
@@ -117,9 +131,17 @@ struct BatchPlan {
     std::vector<PagePlan> pplan;           // per page
     std::vector<OutPlan> oplan;            // per chunk
     std::vector<uint64_t> ba_bm;           // per BaJob: its bitmaps and tile counts (scratch)
+    // kept dictionaries: the kept chunks in chunk order, each chunk's entry in `keeps` (-1: not kept), and the
+    // device tables DevKeep[keeps.size()] and int keep_of[n_chunks] behind the other metadata (bound by bind_batch)
+    std::vector<KeepPlan> keeps;
+    std::vector<int32_t> keep_of;
+    std::vector<DevKeep> dkeeps;
+    size_t off_keeps = 0, off_keepof = 0;
 };
 
-void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const PfOpts& opts, BatchPlan& p);
+// keep: one flag per chunk (pf_decode_row_group_dict), nullptr: none is kept -- the plan of pf_decode_row_group.
+void plan_batch(const pf_chunk_desc* cds, int n_chunks, size_t n_bytes, const PfOpts& opts, BatchPlan& p,
+                const uint8_t* keep = nullptr);
 void bind_batch(BatchPlan& p, const ArenaBases& a);
 
 // The predicates of a filtered decode, validated and packed for the device: the DevPred table and, behind it, the

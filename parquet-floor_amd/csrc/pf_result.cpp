@@ -129,7 +129,8 @@ template <class T> T* shifted(T* q, int64_t d) {   // into the twin arena; nullp
 }
 }  // namespace
 
-FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_info* info, pf_selection_info* sel_info) {
+FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_info* info, pf_selection_info* sel_info,
+                         pf_dict_info* dinfo) {
     FirstError err;
     const DevChunkResult* r = in.res;
     size_t wi = 0;
@@ -159,6 +160,30 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
         ci.d_list_validity = ck.list_validity;
         ci.d_def_levels = ck.def_levels;
         ci.d_rep_levels = ck.rep_levels;
+        if (dinfo) dinfo[c] = pf_dict_info{};
+        const int32_t k = p.keep_of.empty() ? -1 : p.keep_of[size_t(c)];
+        if (k >= 0) {   // kept dictionary: `values` are indices; the dictionary has the chars
+            const KeepPlan& kp = p.keeps[size_t(k)];
+            ci.width = kp.index_width;
+            ci.num_chars = 0;
+            ci.d_offsets = nullptr;
+            ci.d_chars = nullptr;
+            if (dinfo) {
+                pf_dict_info& di = dinfo[c];
+                di.kept = 1;
+                di.index_width = kp.index_width;
+                di.n_entries = kp.n_entries;
+                di.width = kp.width;
+                if (size_t(k) < p.dkeeps.size()) {
+                    di.d_values = p.dkeeps[size_t(k)].d_values;
+                    di.d_offsets = p.dkeeps[size_t(k)].d_offsets;
+                }
+                if (in.keeps && kp.width == 0) {
+                    di.num_chars = std::max<int64_t>(in.keeps[k].num_chars, 0);
+                    di.d_chars = in.keeps[k].d_chars;
+                }
+            }
+        }
         if (wi < in.n_wins && in.wins[wi].chunk == c) {   // the window's view (chunks ascend in wins)
             const DevWinRes& w = in.wres[wi++];
             if (ci.status == 0 && w.status != 0) ci.status = w.status;
@@ -202,7 +227,8 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
     return err;
 }
 
-BatchLayout batch_layout(const BatchPlan& p, const std::vector<pf_column_info>& info, const void* d_chars) {
+BatchLayout batch_layout(const BatchPlan& p, const std::vector<pf_column_info>& info, const void* d_chars,
+                         const std::vector<pf_dict_info>* dicts) {
     BatchLayout b{};
     b.out = p.out_bytes;
     b.bits_off = align_up(b.out, 256);
@@ -216,6 +242,12 @@ BatchLayout batch_layout(const BatchPlan& p, const std::vector<pf_column_info>& 
             bound += align_up(size_t(ci.num_chars), 256);
         }
     }
+    if (dicts)
+        for (const pf_dict_info& di : *dicts)
+            if (di.kept && di.d_chars && di.num_chars > 0) {
+                hi = std::max(hi, size_t(reinterpret_cast<uintptr_t>(di.d_chars) - c0) + size_t(di.num_chars));
+                bound += align_up(size_t(di.num_chars), 256);
+            }
     b.chars = hi;   // bytes copied: the arena's used extent (depends on the order k_scan placed the chunks)
     // buffer size: an order-independent bound, so equal batches always need equal buffers
     b.total = b.chars_off + std::max(hi, bound);
@@ -244,6 +276,19 @@ pf_column_info rebase_info(const BatchLayout& b, const ArenaPtrs& a, const void*
     rb(ci.d_def_levels);
     rb(ci.d_rep_levels);
     return ci;
+}
+
+pf_dict_info rebase_dict(const BatchLayout& b, const ArenaPtrs& a, const void* host, pf_dict_info di) {
+    di.d_values = rebase(b, a, host, di.d_values);
+    di.d_offsets = static_cast<const int32_t*>(rebase(b, a, host, di.d_offsets));
+    di.d_chars = static_cast<const uint8_t*>(rebase(b, a, host, di.d_chars));
+    return di;
+}
+
+void dict_copy_items(const pf_dict_info& di, const pf_column_out& o, CopyItem it[3]) {
+    it[0] = {o.values, o.values_cap, di.d_values, size_t(di.n_entries) * size_t(di.width)};
+    it[1] = {o.offsets, o.offsets_cap, di.d_offsets, di.d_offsets ? 4 * size_t(di.n_entries + 1) : 0};
+    it[2] = {o.chars, o.chars_cap, di.d_chars, size_t(di.num_chars)};
 }
 
 void copy_items(const pf_column_info& ci, const pf_column_out& o, CopyItem it[8]) {

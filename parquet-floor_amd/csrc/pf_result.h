@@ -84,6 +84,7 @@ struct BatchResults {
     const DevSelHead* sel_head;
     const DevSelChunk* sel_chunks;   // [n_chunks]
     const int32_t* sel_rows;         // SelBufs.rows
+    const DevKeep* keeps = nullptr;  // [p.keeps.size()] as the device left them (d_chars, num_chars); nullptr: none kept
 };
 struct FirstError {
     int code = PF_OK;
@@ -92,13 +93,18 @@ struct FirstError {
 // info[n_chunks]: the decode's view; the window's where the decode is OK and the window is not an identity; the
 // selection's over that. A failed stage's status stands, the earliest stage first. *sel_info is written for a filtered
 // batch with at least one chunk.
-FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_info* info, pf_selection_info* sel_info);
+// dinfo[n_chunks] (optional): every chunk's pf_dict_info; a kept chunk's info has width = its index width, no offsets
+// or chars and num_chars = 0.
+FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_info* info, pf_selection_info* sel_info,
+                         pf_dict_info* dinfo = nullptr);
 
 // Host layout of pf_copy_batch_async: [out arena | bits arena | chars arena], each 256-B aligned.
 struct BatchLayout {
     size_t out, bits_off, bits, chars_off, chars, total;
 };
-BatchLayout batch_layout(const BatchPlan& p, const std::vector<pf_column_info>& info, const void* d_chars);
+// dicts (optional): the kept dictionaries, whose chars lie in the chars arena too.
+BatchLayout batch_layout(const BatchPlan& p, const std::vector<pf_column_info>& info, const void* d_chars,
+                         const std::vector<pf_dict_info>* dicts = nullptr);
 // A device pointer into one of the three arenas as the host address of the same byte in a batch copy at `host`
 // (an arena's end included); nullptr for nullptr and for a pointer outside every arena.
 struct ArenaPtrs {
@@ -106,6 +112,7 @@ struct ArenaPtrs {
 };
 const void* rebase(const BatchLayout& b, const ArenaPtrs& a, const void* host, const void* q);
 pf_column_info rebase_info(const BatchLayout& b, const ArenaPtrs& a, const void* host, pf_column_info ci);
+pf_dict_info rebase_dict(const BatchLayout& b, const ArenaPtrs& a, const void* host, pf_dict_info di);
 
 // The eight arrays of a chunk against the caller's buffers: n bytes from src into dst of cap bytes.
 struct CopyItem {
@@ -116,5 +123,7 @@ struct CopyItem {
     bool wanted() const { return dst && src; }
 };
 void copy_items(const pf_column_info& ci, const pf_column_out& o, CopyItem items[8]);
+// The three arrays of a kept dictionary (values, offsets, chars) against the caller's buffers.
+void dict_copy_items(const pf_dict_info& di, const pf_column_out& o, CopyItem items[3]);
 
 }  // namespace pf

@@ -191,6 +191,12 @@ int enqueue_kernels(pf_ctx* ctx) {
         launch_flat(d_chunks, d_pages, list(L_FLAT), p.n_flat_fixed, p.n_flat_all, p.n_null4, p.n_null8,
                     reinterpret_cast<int*>(meta + p.off_nfbq), pairs(L_CDICT), ctx->opts.flat_dstr ? len(L_CDICT) / 2 : 0, d_res, st,
                     ncaps, ctx->opts.null_stagger);
+    // kept-dictionary chunks: indices, dictionary offsets and chars (nothing for a batch without one)
+    const int n_keeps = int(p.keeps.size());
+    if (n_keeps > 0 && !(skip & 32u))
+        launch_flat_ids(d_chunks, d_pages, pairs(L_IDS), len(L_IDS) / 2, reinterpret_cast<DevKeep*>(meta + p.off_keeps), n_keeps,
+                        reinterpret_cast<const int*>(meta + p.off_keepof), d_res, static_cast<uint8_t*>(ctx->d_chars.p),
+                        ctx->d_chars.cap, used, st);
     EVREC(ctx, ctx->ev[9], st);
     if (!(skip & 64u)) launch_decode(d_chunks, d_pages, list(L_DECODE), len(L_DECODE), p.n_decode_first, d_res, st, DECODE_IDLE_GRID);
     launch_nest_decode(d_chunks, d_pages, pairs(L_NSEG), n_nseg, d_res, st);
@@ -215,6 +221,8 @@ int enqueue_kernels(pf_ctx* ctx) {
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_sel.p, ctx->d_sel.p, ctx->sel_lay.o_up, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipGetLastError());
+    if (n_keeps > 0)   // the kept dictionaries' device-written fields (chars base and size)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_keep.p, meta + p.off_keeps, sizeof(DevKeep) * size_t(n_keeps), hipMemcpyDeviceToHost, st));
     // results + device-written chunk fields (chars base) back to pinned host memory
     const ResLayout& rl = ctx->res_lay;
     if (ctx->zc && ctx->h_res.d) {
@@ -245,6 +253,10 @@ int upload_meta(pf_ctx* ctx) {
     put(p.off_wins, p.snap.wins);
     put(p.off_bajobs, p.bajobs);
     put(p.off_batiles, p.ba_tiles);
+    if (!p.keeps.empty()) {
+        put(p.off_keeps, p.dkeeps);
+        put(p.off_keepof, p.keep_of);
+    }
     for (int l = 0; l < N_LISTS; l++) put(p.off_lists + sizeof(int) * p.list_base[l], p.lists[l]);
     {   // diagnostics: force_serial = k sends every k-th Snappy job to the serial kernel (tests of
         // k_snappy_serial's grid-stride over many jobs; valid streams never fall back)
@@ -443,6 +455,7 @@ int pf_ctx_destroy(pf_ctx* ctx) {
     ctx->h_enc_st.release();
     ctx->h_enc_px.release();
     ctx->h_enc_bloom.release();
+    ctx->h_keep.release();
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_bloom) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_win) if (e) (void)hipEventDestroy(e);
@@ -517,6 +530,7 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     BatchPlan& p = ctx->plan;
     ctx->n_chunks = n_chunks;
     ctx->info.assign(n_chunks, pf_column_info{});
+    ctx->dinfo.assign(n_chunks, pf_dict_info{});
     ctx->reruns = 0;
     ctx->timing_valid = false;
     // stage "h2d" (ev[0] -> ev[1]): the input copy when there is one, the metadata upload and the
@@ -530,7 +544,7 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
         d_bytes = static_cast<const uint8_t*>(ctx->d_in.p);
     }
     mark();
-    plan_batch(cds, n_chunks, n_bytes, ctx->opts, p);
+    plan_batch(cds, n_chunks, n_bytes, ctx->opts, p, ctx->keep_flags.empty() ? nullptr : ctx->keep_flags.data());
     mark();
     // ---- arenas ----
     const ArenaNeeds need = arena_needs(p, ctx->chars_need, twins);
@@ -571,6 +585,7 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
     HIPCHK(ctx, ctx->h_meta.ensure(p.meta_bytes));
     ctx->res_lay = res_layout(n_chunks);
     HIPCHK(ctx, ctx->h_res.ensure(ctx->res_lay.total));
+    if (!p.keeps.empty()) HIPCHK(ctx, ctx->h_keep.ensure(sizeof(DevKeep) * p.keeps.size()));
     mark();
     auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
     bind_batch(p, ArenaBases{addr(d_bytes), addr(ctx->d_scratch.p), addr(ctx->d_out.p), addr(ctx->d_bits.p), addr(ctx->d_meta.p),
@@ -596,10 +611,12 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
 
 // pf_decode_row_group (windows == nullptr), pf_decode_row_group_rows and pf_decode_row_group_filter (n_preds > 0).
 int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows, const pf_predicate* preds,
-                 int n_preds, const uint8_t* bytes, size_t n_bytes, int bytes_on_device) {
+                 int n_preds, const uint8_t* bytes, size_t n_bytes, int bytes_on_device, const uint8_t* keep = nullptr) {
     if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
     if (n_chunks < 0 || (n_chunks > 0 && (!cds || !bytes))) return fail(ctx, PF_ERR_INVALID_ARG, "bad arguments");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "previous decode not waited for");
+    ctx->keep_flags.clear();
+    if (keep && n_chunks > 0) ctx->keep_flags.assign(keep, keep + n_chunks);   // (copied, like the descriptors)
     for (int c = 0; windows && c < n_chunks; c++)
         if (windows[c].skip_rows < 0 || windows[c].take_rows < -1)
             return fail(ctx, PF_ERR_INVALID_ARG, "row window: negative skip_rows, or take_rows below -1");
@@ -629,6 +646,11 @@ extern "C" {
 int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* bytes, size_t n_bytes,
                         int bytes_on_device) {
     return decode_batch(ctx, cds, n_chunks, nullptr, nullptr, 0, bytes, n_bytes, bytes_on_device);
+}
+
+int pf_decode_row_group_dict(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* keep, const uint8_t* bytes,
+                             size_t n_bytes, int bytes_on_device) {
+    return decode_batch(ctx, cds, n_chunks, nullptr, nullptr, 0, bytes, n_bytes, bytes_on_device, keep);
 }
 
 int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows,
@@ -722,7 +744,8 @@ int pf_wait(pf_ctx* ctx) {
         br.sel_head = filtered ? reinterpret_cast<const DevSelHead*>(hsel + ctx->sel_lay.o_head) : nullptr;
         br.sel_chunks = filtered ? reinterpret_cast<const DevSelChunk*>(hsel + ctx->sel_lay.o_sc) : nullptr;
         br.sel_rows = ctx->sel.rows;
-        const FirstError fe = assemble_info(ctx->plan, br, ctx->info.data(), &ctx->sel_info);
+        br.keeps = ctx->plan.keeps.empty() ? nullptr : static_cast<const DevKeep*>(ctx->h_keep.p);
+        const FirstError fe = assemble_info(ctx->plan, br, ctx->info.data(), &ctx->sel_info, ctx->dinfo.data());
         if (fe.code != PF_OK) fail(ctx, fe.code, fe.msg);
         ctx->pending = false;
         ctx->timing_valid = true;
@@ -791,7 +814,7 @@ int pf_copy_columns_async(pf_ctx* ctx, int n, const int* chunks, const pf_column
 
 namespace {
 // Host layout of pf_copy_batch_async for the last decode (pf_result.h).
-BatchLayout last_layout(const pf_ctx* ctx) { return batch_layout(ctx->plan, ctx->info, ctx->d_chars.p); }
+BatchLayout last_layout(const pf_ctx* ctx) { return batch_layout(ctx->plan, ctx->info, ctx->d_chars.p, &ctx->dinfo); }
 }  // namespace
 
 int pf_batch_bytes(pf_ctx* ctx, size_t* bytes) {
@@ -862,6 +885,42 @@ int pf_column_info_host(pf_ctx* ctx, int chunk, const void* host, pf_column_info
     return PF_OK;
 }
 
+int pf_dict_info_get(pf_ctx* ctx, int chunk, pf_dict_info* out) {
+    if (!ctx || !out) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
+    *out = ctx->dinfo[chunk];
+    return PF_OK;
+}
+
+int pf_dict_info_host(pf_ctx* ctx, int chunk, const void* host, pf_dict_info* out) {
+    if (!ctx || !out || !host) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
+    if (ctx->twins()) return fail(ctx, PF_ERR_STATE, "the last decode had row windows or a row filter: no batch copy");
+    *out = rebase_dict(last_layout(ctx), ArenaPtrs{ctx->d_out.p, ctx->d_bits.p, ctx->d_chars.p}, host, ctx->dinfo[chunk]);
+    return PF_OK;
+}
+
+int pf_copy_dictionary(pf_ctx* ctx, int chunk, const pf_column_out* o) {
+    if (!ctx || !o) return fail(ctx, PF_ERR_INVALID_ARG, "null arg");
+    if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
+    if (chunk < 0 || chunk >= ctx->n_chunks) return fail(ctx, PF_ERR_INVALID_ARG, "chunk index out of range");
+    const pf_dict_info& di = ctx->dinfo[chunk];
+    if (!di.kept) return fail(ctx, PF_ERR_STATE, "the chunk's dictionary was not kept");
+    if (ctx->info[chunk].status != 0) return fail(ctx, ctx->info[chunk].status, "chunk failed to decode");
+    CopyItem items[3];
+    dict_copy_items(di, *o, items);
+    for (const CopyItem& it : items)
+        if (it.wanted() && it.n > it.cap) return fail(ctx, PF_ERR_CAPACITY, "dictionary buffer too small");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (const CopyItem& it : items)
+        if (it.wanted() && it.n) HIPCHK(ctx, hipMemcpyAsync(it.dst, it.src, it.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_copy, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev_copy));
+    return PF_OK;
+}
+
 int pf_sync(pf_ctx* ctx) {
     if (!ctx) return fail(nullptr, PF_ERR_INVALID_ARG, "null ctx");
     if (ctx->pending) return fail(ctx, PF_ERR_STATE, "call pf_wait first");
@@ -881,6 +940,7 @@ int begin_oneshot(pf_ctx* ctx, bool drop_batch) {
     if (drop_batch) {
         ctx->n_chunks = 0;
         ctx->info.clear();
+        ctx->dinfo.clear();
         ctx->tables_from_decode = false;
     }
     return PF_OK;

@@ -107,6 +107,12 @@ class SelectionInfo(C.Structure):
     _fields_ = [("rows_in", C.c_int64), ("rows_selected", C.c_int64), ("d_rows", C.c_void_p), ("status", C.c_int32)]
 
 
+class DictInfo(C.Structure):
+    _fields_ = [("kept", C.c_int32), ("index_width", C.c_int32), ("n_entries", C.c_int64), ("width", C.c_int32),
+                ("pad", C.c_int32), ("num_chars", C.c_int64), ("d_values", C.c_void_p), ("d_offsets", C.c_void_p),
+                ("d_chars", C.c_void_p)]
+
+
 class PfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -162,6 +168,10 @@ def _load(path):
         "pf_memcpy_h2d": ([vp, vp, vp, sz], C.c_int),
         "pf_decode_row_group": ([vp, C.POINTER(ChunkDesc), i32, vp, sz, i32], C.c_int),
         "pf_decode_row_group_rows": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), vp, sz, i32], C.c_int),
+        "pf_decode_row_group_dict": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(C.c_uint8), vp, sz, i32], C.c_int),
+        "pf_dict_info_get": ([vp, i32, C.POINTER(DictInfo)], C.c_int),
+        "pf_dict_info_host": ([vp, i32, vp, C.POINTER(DictInfo)], C.c_int),
+        "pf_copy_dictionary": ([vp, i32, C.POINTER(ColumnOut)], C.c_int),
         "pf_debug_window": ([vp, C.POINTER(C.c_float), C.POINTER(C.c_int)], C.c_int),   # (diagnostics, not in pfloor.h)
         "pf_decode_row_group_filter": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), C.POINTER(Predicate), i32, vp, sz,
                                         i32], C.c_int),

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._native import (ChunkDesc, ChunkRows, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, PageDesc, PageLocation,
+from ._native import (ChunkDesc, ChunkRows, ColumnIndex, ColumnInfo, ColumnMeta, ColumnOut, DictInfo, PageDesc, PageLocation,
                       Predicate, RowWindow, ScanChunk, ScanResult, SelectionInfo, check, lib)
 
 CONVERTED_UTF8, CONVERTED_ENUM, CONVERTED_JSON = 0, 4, 19
@@ -399,16 +399,26 @@ class GpuDecoder:
             self._staging = PinnedBuffer(self.h, max(nbytes, 1 << 20))
         return self._staging
 
-    def decode(self, descs, buf_ptr, nbytes, on_device=False, windows=None, predicates=None):
+    def decode(self, descs, buf_ptr, nbytes, on_device=False, windows=None, predicates=None, keep=None):
         """descs: ChunkDesc list, or a prebuilt ctypes ChunkDesc array (no per-call copy). windows: one (skip_rows,
         take_rows) per chunk (take -1: to the end): the results are cut to those rows on the GPU
         (pf_decode_row_group_rows); None: pf_decode_row_group. predicates: a list of (chunk, op, lo, hi) -- chunk an
         index into descs, op a PF_PRED_* code, lo / hi the PLAIN bytes of a bound or None (pfloor.predicate.bind makes
         them): a conjunction evaluated on the GPU, every chunk compacted to the matching rows
-        (pf_decode_row_group_filter; selection() has the row numbers). None: no filter."""
+        (pf_decode_row_group_filter; selection() has the row numbers). None: no filter. keep: one bool per chunk
+        (pf_decode_row_group_dict): a chunk that is dictionary-encoded throughout comes back as indices + dictionary
+        (fetch, materialize), any other as ever; not together with windows or predicates (ValueError)."""
+        if keep is not None and (windows is not None or predicates is not None):
+            raise ValueError("keep= takes no windows and no predicates")
+        if keep is not None and len(keep) != len(descs):
+            raise ValueError("one keep flag per chunk")
         arr = descs if isinstance(descs, C.Array) else (ChunkDesc * max(1, len(descs)))(*descs)
         self._keep = arr
-        if predicates is not None:
+        if keep is not None:
+            flags = (C.c_uint8 * max(1, len(keep)))(*[1 if k else 0 for k in keep])
+            check(lib().pf_decode_row_group_dict(self.h, arr, len(descs), flags, C.c_void_p(buf_ptr), nbytes, 1 if on_device else 0),
+                  self.h, "pf_decode_row_group_dict")
+        elif predicates is not None:
             if windows is not None and len(windows) != len(descs):
                 raise ValueError("one window per chunk")
             win = None if windows is None else (RowWindow * max(1, len(windows)))(*[RowWindow(int(s), int(t)) for s, t in windows])
@@ -477,6 +487,12 @@ class GpuDecoder:
         ci = ColumnInfo()
         check(lib().pf_column_info_get(self.h, i, C.byref(ci)), self.h, "pf_column_info_get")
         return ci
+
+    def dict_info(self, i):
+        """pf_dict_info of chunk i of the last decode, after wait(): .kept is 0 unless the chunk's dictionary was kept."""
+        di = DictInfo()
+        check(lib().pf_dict_info_get(self.h, i, C.byref(di)), self.h, "pf_dict_info_get")
+        return di
 
     def snappy_decompress(self, data: bytes, cap=None):
         """Raw Snappy buffer -> bytes on the GPU (K1 kernels). Returns (bytes, used_fallback)."""
@@ -600,7 +616,20 @@ class GpuDecoder:
                             raise AssertionError("array missing from the batch copy")
                         o = ptr - base
                         return host[o:o + nbytes].copy().view(dtype)
-                    if ptype == 6:
+                    di = DictInfo()
+                    check(L.pf_dict_info_host(self.h, i, buf.ptr, C.byref(di)), self.h, "pf_dict_info_host")
+                    if di.kept:
+                        g["indices"] = (cut(ci.d_values, ns * ci.width, INDEX_DTYPES[ci.width]) if ns
+                                        else np.zeros(0, INDEX_DTYPES[ci.width]))
+                        d = {"n_entries": di.n_entries, "width": di.width}
+                        if di.width:
+                            dict_bytes = di.n_entries * di.width
+                            d["values"] = cut(di.d_values, dict_bytes) if dict_bytes else np.zeros(0, np.uint8)
+                        else:
+                            d["offsets"] = cut(di.d_offsets, 4 * (di.n_entries + 1), np.int32)
+                            d["chars"] = cut(di.d_chars, di.num_chars) if di.num_chars else np.zeros(0, np.uint8)
+                        g["dictionary"] = d
+                    elif ptype == 6:
                         g["offsets"] = cut(ci.d_offsets, 4 * (ns + 1), np.int32)
                         g["chars"] = cut(ci.d_chars, ci.num_chars) if ci.num_chars else np.zeros(0, np.uint8)
                     else:
@@ -635,6 +664,29 @@ class GpuDecoder:
             setattr(o, name, a.ctypes.data if a.size else None)
             setattr(o, name + "_cap", a.nbytes)
 
+        di = self.dict_info(i)
+        if di.kept:   # indices (in `values`) + the dictionary's own arrays
+            want("values", ns, INDEX_DTYPES[ci.width])
+            d, do = {"n_entries": di.n_entries, "width": di.width}, ColumnOut()
+
+            def dwant(name, n, dtype=np.uint8):
+                a = np.zeros(max(n, 0), dtype=dtype)
+                d[name] = a
+                setattr(do, name, a.ctypes.data if a.size else None)
+                setattr(do, name + "_cap", a.nbytes)
+            if di.width:
+                dwant("values", di.n_entries * di.width)
+            else:
+                dwant("offsets", di.n_entries + 1, np.int32)
+                dwant("chars", di.num_chars)
+            check(lib().pf_copy_dictionary(self.h, i, C.byref(do)), self.h, "pf_copy_dictionary")
+            if max_def > 0:
+                want("validity", (ns + 7) // 8)
+            check(lib().pf_copy_column(self.h, i, C.byref(o)), self.h, "pf_copy_column")
+            arrs["indices"] = arrs.pop("values")
+            out.update(arrs)
+            out["dictionary"] = d
+            return out
         if physical_type == 6:
             want("offsets", ns + 1, np.int32)
             want("chars", ci.num_chars)
@@ -653,7 +705,53 @@ class GpuDecoder:
         return out
 
 
-def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, rows=None, where=None):
+INDEX_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32}
+
+
+def materialize(arrays, physical_type):
+    """A kept chunk (fetch / fetch_batch: "indices" + "dictionary") expanded on the host into the canonical arrays of
+    include/pfloor.h: values[s] = dictionary[indices[s]] where the validity bit is set, zero bytes (a zero-length
+    string) where it is not; BYTE_ARRAY offsets and chars are rebuilt in slot order. numpy only. Arrays of a chunk
+    that was not kept are returned as they are."""
+    if "indices" not in arrays:
+        return arrays
+    out = {k: v for k, v in arrays.items() if k not in ("indices", "dictionary")}
+    d = arrays["dictionary"]
+    idx = np.asarray(arrays["indices"]).astype(np.int64)
+    ns = len(idx)
+    v = arrays.get("validity")
+    valid = np.unpackbits(np.asarray(v, np.uint8), bitorder="little")[:ns].astype(bool) if v is not None else np.ones(ns, bool)
+    n_entries = int(d["n_entries"])
+    if valid.any() and (n_entries == 0 or int(idx[valid].max()) >= n_entries):
+        raise ValueError("materialize: an index outside the dictionary")
+    if physical_type == 6:
+        doffs = np.asarray(d["offsets"], np.int64)
+        dchars = np.asarray(d["chars"], np.uint8)
+        lens = np.zeros(ns, np.int64)
+        lens[valid] = (doffs[1:] - doffs[:-1])[idx[valid]]
+        offs = np.zeros(ns + 1, np.int64)
+        np.cumsum(lens, out=offs[1:])
+        if offs[-1] > 0x7fffffff:
+            raise ValueError("materialize: more than 2^31 - 1 chars")
+        starts = np.zeros(ns, np.int64)
+        starts[valid] = doffs[:-1][idx[valid]]
+        src = np.repeat(starts - offs[:-1], lens) + np.arange(int(offs[-1]), dtype=np.int64)
+        out["offsets"] = offs.astype(np.int32)
+        out["chars"] = dchars[src] if len(src) else np.zeros(0, np.uint8)
+        out["num_chars"] = int(offs[-1])
+        out["width"] = 0
+    else:
+        w = int(d["width"])
+        dv = np.asarray(d["values"], np.uint8).reshape(n_entries, w)
+        vals = np.zeros((ns, w), np.uint8)
+        vals[valid] = dv[idx[valid]]
+        out["values"] = vals.ravel()
+        out["num_chars"] = 0
+        out["width"] = w
+    return out
+
+
+def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, rows=None, where=None, dictionaries=False):
     """Decode the selected chunks of a file on the GPU: {(rg, col): arrays}. One batch.
     rows=(lo, hi): rows [lo, hi) of ONE row group (row_groups names it; default 0), counted within it: only the
     pages its OffsetIndex selects are read and uploaded, and the arrays are cut to the rows on the GPU.
@@ -661,7 +759,11 @@ def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, row
     Bloom filters prune first (ParquetFile.prune_row_group), the predicates are evaluated on the GPU and the arrays
     hold the matching rows only. "_selection" = (rows_in, row numbers within the row group as np.int64), "_range" =
     the rows that were decoded, None when the row group was skipped (no chunk is returned then). A predicate column
-    outside `columns` is decoded and not returned."""
+    outside `columns` is decoded and not returned.
+    dictionaries=True (whole-file decodes only): every chunk that is dictionary-encoded throughout comes back as
+    "indices" + "dictionary" (GpuDecoder.decode(keep=...)); materialize() expands one on the host."""
+    if dictionaries and (rows is not None or where is not None):
+        raise ValueError("dictionaries=True reads whole row groups: no rows= and no where=")
     with ParquetFile(path) as pf:
         rgs = list(range(pf.num_row_groups)) if row_groups is None else list(row_groups)
         cols = list(range(pf.num_columns)) if columns is None else list(columns)
@@ -705,7 +807,8 @@ def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, row
                 if n:
                     pf.read_into(s, n, buf.ptr.value + off)
                 descs.append(pf.chunk_desc(rg, col, off))
-            dec.decode(descs, buf.ptr.value, max(total, 1))
+            extra = {"keep": [True] * len(descs)} if dictionaries else {}
+            dec.decode(descs, buf.ptr.value, max(total, 1), **extra)
             rc = dec.wait()
             out = {}
             for i, (rg, col, *_r) in enumerate(items):

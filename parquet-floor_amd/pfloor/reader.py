@@ -147,8 +147,13 @@ def stringifier(col):
     return _default_stringify
 
 
+_UNSET = object()
+
+
 class _ColumnCursor:
-    """ColumnReader over one decoded chunk: current definition/repetition level, value, consume()."""
+    """ColumnReader over one decoded chunk: current definition/repetition level, value, consume(). Over a kept chunk
+    ("indices" + "dictionary", GpuDecoder.decode(keep=...)) every dictionary entry is converted once, when a row first
+    uses it, and a row costs one list lookup."""
 
     def __init__(self, col, arrays):
         self.col = col
@@ -166,7 +171,17 @@ class _ColumnCursor:
             self.valid = (np.unpackbits(v, bitorder="little")[:self.n].astype(bool) if v is not None
                           else np.ones(self.n, bool))
         pt = col.physical_type
-        if pt in (6,):
+        self.indices = arrays.get("indices")
+        if self.indices is not None:
+            d = arrays["dictionary"]
+            self.dict_n, self.dict_width = int(d["n_entries"]), int(d["width"])
+            if pt == 6:
+                self.dict_offsets = d["offsets"]
+                self.dict_chars = d["chars"].tobytes()
+            else:
+                self.dict_values = d["values"]
+            self.converted = [_UNSET] * self.dict_n
+        elif pt in (6,):
             self.offsets = arrays["offsets"]
             self.chars = arrays["chars"].tobytes()
         else:
@@ -192,19 +207,33 @@ class _ColumnCursor:
         w = self.a["width"]
         return self.values[s * w:(s + 1) * w].tobytes()
 
+    def _dict_raw(self, i):
+        if self.col.physical_type == 6:
+            return self.dict_chars[self.dict_offsets[i]:self.dict_offsets[i + 1]]
+        w = self.dict_width
+        return self.dict_values[i * w:(i + 1) * w].tobytes()
+
+    def _convert(self, raw):
+        pt = self.col.physical_type
+        if pt in (6, 7, 3):
+            return self.strf(raw)
+        if pt == 0:
+            return bool(raw[0])
+        if self.fmt:
+            return struct.unpack(self.fmt, raw)[0]
+        raise IllegalArgumentException(f"Unsupported type: {self.col}")
+
     def read_value(self):
         """ParquetReader.readValue (ParquetReader.java:141-168)."""
         col = self.col
         if self.definition_level() == col.max_def:
-            pt = col.physical_type
-            raw = self._raw(self.slot)
-            if pt in (6, 7, 3):
-                return self.strf(raw)
-            if pt == 0:
-                return bool(raw[0])
-            if self.fmt:
-                return struct.unpack(self.fmt, raw)[0]
-            raise IllegalArgumentException(f"Unsupported type: {col}")
+            if self.indices is not None:
+                i = int(self.indices[self.slot])
+                v = self.converted[i]
+                if v is _UNSET:
+                    v = self.converted[i] = self._convert(self._dict_raw(i))
+                return v
+            return self._convert(self._raw(self.slot))
         return None
 
     def consume(self):
@@ -233,7 +262,8 @@ class RowGroupPipeline:
     back compacted to the matching rows. A predicate column that is not among `columns` is decoded and not returned.
     `selections[i]` = (rows_in, rows_selected) of row_groups[i] once taken; `bytes_read` counts the chunk bytes read."""
 
-    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None, where=None):
+    def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None, where=None, dictionaries=False):
+        self.dictionaries = bool(dictionaries)   # row groups read whole keep their eligible chunks' dictionaries
         if not devices:
             raise ValueError("devices must not be empty")
         self.reader = reader
@@ -292,7 +322,8 @@ class RowGroupPipeline:
                 if n:
                     self.reader.read_into(s, n, buf.ptr.value + off)
                 descs.append(self.reader.chunk_desc(rg, col, off))
-            dec.decode(descs, buf.ptr.value, max(total, 1))
+            extra = {"keep": [True] * len(descs)} if self.dictionaries else {}
+            dec.decode(descs, buf.ptr.value, max(total, 1), **extra)
             self.inflight[i] = dec
         except Exception as e:   # surfaces when row group i is reached, as readNextRowGroup would raise it
             self.inflight[i] = e
@@ -330,11 +361,12 @@ class ParquetReader:
 
     # --- static factories (ParquetReader.java:47-84) ---
     @staticmethod
-    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None):
-        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices, rows, where))
+    def streamContent(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None, dictionaries=False):
+        return ParquetReader.stream(ParquetReader.spliterator(file, hydratorSupplier, columns, device, devices, rows, where,
+                                                              dictionaries))
 
     @staticmethod
-    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None):
+    def spliterator(file, hydratorSupplier, columns=None, device=0, devices=None, rows=None, where=None, dictionaries=False):
         """devices: GPUs to deal the row groups over (default [device]); rows stay in file order.
         rows=(lo, hi): only rows lo .. hi-1 of the file (0 <= lo <= hi <= num_rows): row groups wholly outside are
         neither read nor decoded, the two edge row groups are read by page and cut on the GPU, inner ones as ever.
@@ -342,9 +374,12 @@ class ParquetReader:
         Bloom filters prune every row group (ParquetFile.prune_row_group: a skipped one is neither read nor decoded);
         the rest are read by page over what remains, filtered on the GPU and compacted there, so only matching rows
         cross the link. A predicate column outside `columns` is decoded and never passed to the Hydrator. A projected
-        or predicate column with repetition is an IllegalArgumentException. `filter_stats` counts what happened."""
+        or predicate column with repetition is an IllegalArgumentException. `filter_stats` counts what happened.
+        dictionaries=True: a row group that is read whole (no rows= edge, no where=) keeps the dictionary of every chunk
+        that is dictionary-encoded throughout: indices and dictionary cross the link instead of expanded values, and
+        each dictionary entry is converted once per row group. Rows, call order and exceptions are those of the default."""
         column_set = frozenset() if columns is None else frozenset(columns)
-        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices, rows, where)
+        return ParquetReader(str(file), column_set, hydratorSupplier, device, devices, rows, where, dictionaries)
 
     @staticmethod
     def stream(reader):
@@ -383,7 +418,8 @@ class ParquetReader:
         return f
 
     # --- instance (ParquetReader.java:119-131) ---
-    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None, rows=None, where=None):
+    def __init__(self, path, column_names, hydrator_supplier, device=0, devices=None, rows=None, where=None, dictionaries=False):
+        self._dictionaries = bool(dictionaries)
         try:
             self.reader = ParquetFile(path)
         except Exception as e:
@@ -460,7 +496,8 @@ class ParquetReader:
             raise RuntimeError("Illegal row group of 0 rows")
         if self._pipe is None:
             self._pipe = RowGroupPipeline(self.reader, self.columns, [v[0] for v in self._visits], self._devices,
-                                          windows=[v[1] for v in self._visits], where=self._where)
+                                          windows=[v[1] for v in self._visits], where=self._where,
+                                          dictionaries=self._dictionaries)
         arrays = self._pipe.take(self._pos)
         self.cursors = [_ColumnCursor(c, a) for c, a in zip(self.columns, arrays)]
         self.current_row_group_size = self.reader.row_group_rows(rg) if win is None else win[1] - win[0]
