@@ -280,7 +280,8 @@ int pf_copy_selection(pf_ctx* ctx, int32_t* rows, size_t cap_bytes);
  * Indices and dictionary arrays live in the batch's out and chars arenas, so pf_batch_bytes, pf_copy_batch_async and
  * pf_column_info_host work after such a decode (the batch is that much smaller); pf_dict_info_host rebases as
  * pf_column_info_host does. The dictionary chars count towards the chars arena's need (an overflow reruns the batch).
- * pf_decode_row_group_rows and _filter take no keep flags: windows or predicates over kept chunks are not done. */
+ * pf_decode_row_group_rows and _filter take no keep flags: pf_decode_row_group_dict_filter (below) windows and filters
+ * kept chunks. */
 int pf_decode_row_group_dict(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const uint8_t* keep,
                              const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
 typedef struct pf_dict_info {
@@ -299,6 +300,35 @@ typedef struct pf_dict_info {
 int pf_dict_info_get(pf_ctx* ctx, int chunk, pf_dict_info* out);
 /* After pf_copy_batch_async + pf_sync: the same with the pointers rebased into the host copy. */
 int pf_dict_info_host(pf_ctx* ctx, int chunk, const void* host, pf_dict_info* out);
+/* Windows and predicates over kept dictionaries: pf_decode_row_group_filter with the keep flags of
+ * pf_decode_row_group_dict. keep == NULL is pf_decode_row_group_filter, call for call; windows == NULL and n_preds == 0
+ * is pf_decode_row_group_dict, batch copies included. The call errors are those of pf_decode_row_group_filter.
+ * Eligibility, index_width and pf_dict_info are those of pf_decode_row_group_dict. A chunk that is asked for and not
+ * eligible is decoded, windowed and filtered expanded, exactly as pf_decode_row_group_filter does it; never an error.
+ * A kept chunk goes through both stages as a fixed-width column of index_width bytes with a validity bitmap:
+ *   window   pf_column_info describes the window's slots: width = index_width, d_values = the window's indices (0 in a
+ *            null slot), validity from bit 0 with the tail bits of the last byte zero, d_offsets = d_chars = NULL,
+ *            num_chars = 0. The window's statuses are those of pf_decode_row_group_rows.
+ *   filter   a PF_PRED_RANGE on a kept chunk is evaluated once per dictionary entry and looked up per row through the
+ *            indices; the row mask is bit for bit the mask the predicate gives on the expanded chunk (a null row matches
+ *            only IS_NULL, a NaN entry matches no bound, -0.0 equals +0.0, bytes compare unsigned with a proper prefix
+ *            first). IS_NULL / NOT_NULL read the validity only and stay legal on kept INT96 and FIXED_LEN_BYTE_ARRAY
+ *            chunks; PF_PRED_RANGE on those stays PF_ERR_UNSUPPORTED_TYPE. Indices and validity of every kept chunk
+ *            are compacted through the row numbers: num_rows = num_entries = num_slots = rows_selected, num_values =
+ *            the set validity bits, num_chars = 0.
+ * The dictionary is never windowed, compacted or moved: pf_dict_info_get and pf_copy_dictionary give what they give
+ * after pf_decode_row_group_dict on the same chunks, every entry in file order, entries no surviving row uses included.
+ * The invariant: a kept chunk's result expanded on the host (values[s] = dict[index[s]] as above) is bit for bit what
+ * pf_decode_row_group_filter returns for that chunk with the same windows and predicates; pf_selection_info and
+ * pf_copy_selection are identical in both.
+ * Errors: an id >= n_entries in a present value gives the chunk the status and error page of the expanding decode; if
+ * the chunk carries a predicate every chunk takes the status (the rule of pf_decode_row_group_filter). An all-null
+ * chunk over an empty dictionary is valid: every RANGE matches nothing, IS_NULL matches every row.
+ * After a decode with a window that is not {0, -1} or any predicate, pf_batch_bytes, pf_copy_batch_async,
+ * pf_column_info_host and pf_dict_info_host return PF_ERR_STATE; use pf_copy_column(s_async) and pf_copy_dictionary. */
+int pf_decode_row_group_dict_filter(pf_ctx* ctx, const pf_chunk_desc* chunks, int n_chunks, const uint8_t* keep,
+                                    const pf_row_window* windows, const pf_predicate* preds, int n_preds,
+                                    const uint8_t* bytes, size_t n_bytes, int bytes_on_device);
 /* The dictionary of a kept chunk into out->values (fixed width) or out->offsets / out->chars (BYTE_ARRAY); the other
  * fields of `out` are ignored. Host buffers, synchronous. PF_ERR_CAPACITY (nothing copied) if a non-NULL buffer is too
  * small; PF_ERR_STATE on a chunk with kept == 0; the chunk's own status if it failed to decode. */

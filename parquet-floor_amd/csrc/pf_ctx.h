@@ -140,6 +140,7 @@ struct pf_ctx {
     pf::DevBuf d_sel;
     pf::HostBuf h_sel;
     pf::SelBufs sel{};
+    pf::SelDictBufs sel_dict{};             // predicates on kept chunks (pf_decode_row_group_dict_filter), and the keep tables
     hipEvent_t ev_sel[2] = {};
     pf_selection_info sel_info{};
     bool filtered() const { return !filt.preds.empty(); }

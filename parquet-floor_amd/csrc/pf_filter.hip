@@ -11,7 +11,7 @@
 // Nothing here uses atomics: every count is a reduction in a fixed order. Sizes only the device knows (rows_in,
 // rows_selected) meet grids sized from the host's capacities; a workgroup past them leaves at once, uniformly.
 #include "pf_launch.h"
-#include "pf_pred.h"
+#include "pf_sel.h"
 
 namespace pf {
 namespace {
@@ -19,11 +19,7 @@ namespace {
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint64_t ul2 __attribute__((ext_vector_type(2)));
 
-constexpr int SB = 256;                           // threads of every kernel
-constexpr int SEL_WORDS = int(SEL_TILE / 64);     // mask words of a tile
-constexpr int SEL_WPW = SEL_WORDS / 4;            // ... of one wave: rows [wave * 64 * SEL_WPW, + 64 * SEL_WPW) of the tile
 constexpr int SEL_RPT = int(SEL_TILE / SB);       // consecutive rows per thread of the length scan
-static_assert(SEL_TILE % 256 == 0 && SEL_TILE >= 256, "a tile is whole mask words for each of four waves");
 
 template <typename T>
 __device__ __forceinline__ T* twin(T* p, int64_t delta) {
@@ -47,7 +43,8 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane) {
 __global__ __launch_bounds__(SB) void k_sel_prep(const DevChunk* __restrict__ chunks, const DevChunkResult* __restrict__ res,
                                                  const DevWinRes* __restrict__ wres, SelBufs f, int n_chunks,
                                                  const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta,
-                                                 int64_t bits_delta) {
+                                                 int64_t bits_delta, const int32_t* __restrict__ keep_of,
+                                                 const DevKeep* __restrict__ keeps) {
     __shared__ int32_t s_status;
     __shared__ int64_t s_rows;
     const int tid = threadIdx.x;
@@ -55,7 +52,9 @@ __global__ __launch_bounds__(SB) void k_sel_prep(const DevChunk* __restrict__ ch
         const DevChunk& ck = chunks[c];
         const DevChunkResult& r = res[c];
         DevSelChunk x{};
-        x.width = ck.width;
+        // a kept chunk (pf_filter_dict.hip) is a fixed-width column of its indices: no offsets and no chars of its own
+        const int32_t kp = keep_of ? keep_of[c] : -1;
+        x.width = kp >= 0 ? keeps[kp].index_width : ck.width;
         x.ptype = ck.ptype;
         x.max_def = ck.max_def;
         int32_t st = r.status;
@@ -80,6 +79,7 @@ __global__ __launch_bounds__(SB) void k_sel_prep(const DevChunk* __restrict__ ch
             x.o_values = ck.values; x.o_validity = ck.validity; x.o_offsets = ck.offsets;
             x.o_chars = const_cast<uint8_t*>(w.chars_src);
         }
+        if (kp >= 0) { x.offsets = nullptr; x.chars = nullptr; x.o_offsets = nullptr; x.o_chars = nullptr; }
         x.n_rows = rows;
         x.status = st;
         f.sc[c] = x;
@@ -115,26 +115,6 @@ __global__ __launch_bounds__(SB) void k_sel_prep(const DevChunk* __restrict__ ch
 
 // ---- k_sel_mask ----------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ bool eval_row(const DevPred& p, const DevSelChunk& c, int64_t r, const uint8_t* __restrict__ blob) {
-    bool present = true;
-    if (c.max_def > 0 && c.validity) present = (c.validity[r >> 3] >> (r & 7)) & 1;
-    if (p.op == PF_PRED_IS_NULL) return !present;
-    if (p.op == PF_PRED_NOT_NULL || !present) return present;
-    const bool has_lo = p.flags & PRED_HAS_LO, has_hi = p.flags & PRED_HAS_HI;
-    switch (p.ptype) {
-    case PF_BOOLEAN: return pred_range_int(c.values[r], has_lo, p.lo_i, has_hi, p.hi_i);
-    case PF_INT32: return pred_range_int(reinterpret_cast<const int32_t*>(c.values)[r], has_lo, p.lo_i, has_hi, p.hi_i);
-    case PF_INT64: return pred_range_int(reinterpret_cast<const int64_t*>(c.values)[r], has_lo, p.lo_i, has_hi, p.hi_i);
-    case PF_FLOAT: return pred_range_real(double(reinterpret_cast<const float*>(c.values)[r]), has_lo, p.lo_f, has_hi, p.hi_f);
-    case PF_DOUBLE: return pred_range_real(reinterpret_cast<const double*>(c.values)[r], has_lo, p.lo_f, has_hi, p.hi_f);
-    case PF_BYTE_ARRAY: {
-        const int32_t a = c.offsets[r], b = c.offsets[r + 1];
-        return pred_range_bytes(c.chars + a, uint32_t(b - a), has_lo, blob + p.lo_off, p.lo_len, has_hi, blob + p.hi_off, p.hi_len);
-    }
-    default: return false;
-    }
-}
-
 __global__ __launch_bounds__(SB) void k_sel_mask(SelBufs f) {
     const int64_t rows_in = f.head->rows_in;   // 0 when the stage failed
     const int64_t tile = blockIdx.x, base = tile * SEL_TILE;
@@ -165,7 +145,7 @@ __global__ __launch_bounds__(SB) void k_sel_mask(SelBufs f) {
 __global__ __launch_bounds__(SB) void k_sel_scan(const uint32_t* in, uint32_t* out, int64_t stride, const DevSelHead* head,
                                                  int by_selected, const DevSelChunk* sc, int64_t* totals) {
     const int b = blockIdx.x;
-    if (sc && (sc[b].status != 0 || sc[b].ptype != PF_BYTE_ARRAY)) return;
+    if (sc && (sc[b].status != 0 || sc[b].ptype != PF_BYTE_ARRAY || !sc[b].o_offsets)) return;   // (kept: no chars)
     const int64_t n = tiles_of(by_selected ? head->rows_selected : head->rows_in);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     in += b * stride;
@@ -213,7 +193,7 @@ __global__ __launch_bounds__(SB) void k_sel_rows(SelBufs f) {
 
 // ---- k_sel_gather --------------------------------------------------------------------------------------------------
 
-// nj output rows from j0 on: dst[j] = src[rows[j]]. Widths 1, 4 and 8: every lane gathers 16 output bytes and stores
+// nj output rows from j0 on: dst[j] = src[rows[j]]. Widths 1, 2, 4 and 8: every lane gathers 16 output bytes and stores
 // them at once (the outputs start 256-byte aligned and j0 is a multiple of SEL_TILE); the rows past the last whole
 // group go one by one. Other widths (INT96, FIXED_LEN_BYTE_ARRAY): one lane per output dword or byte, so the stores
 // are coalesced whatever the width.
@@ -264,6 +244,25 @@ __device__ __forceinline__ void gather_values(const DevSelChunk& c, const int32_
                 for (int k = i; k < nj; k++) d[k] = s[rj[k]];
             }
         }
+    } else if (c.width == 2) {   // (2-byte dictionary indices, FIXED_LEN_BYTE_ARRAY(2))
+        const uint16_t* __restrict__ s = reinterpret_cast<const uint16_t*>(c.values);
+        uint16_t* d = reinterpret_cast<uint16_t*>(c.o_values) + j0;
+        for (int i = tid * 8; i < nj; i += SB * 8) {
+            if (i + 8 <= nj) {
+                uint32_t v[4];
+                #pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    const int4 r = *reinterpret_cast<const int4*>(rj + i + 4 * q);
+                    v[2 * q] = uint32_t(s[r.x]) | uint32_t(s[r.y]) << 16;
+                    v[2 * q + 1] = uint32_t(s[r.z]) | uint32_t(s[r.w]) << 16;
+                }
+                u4 o;
+                o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+                *reinterpret_cast<u4*>(d + i) = o;
+            } else {
+                for (int k = i; k < nj; k++) d[k] = s[rj[k]];
+            }
+        }
     } else if ((c.width & 3) == 0) {
         const uint32_t wq = uint32_t(c.width) >> 2;
         const uint32_t* __restrict__ s = reinterpret_cast<const uint32_t*>(c.values);
@@ -285,7 +284,8 @@ __device__ __forceinline__ void gather_values(const DevSelChunk& c, const int32_
 }
 
 // Grid (tiles, chunk). The workgroups of a chunk stride over its output tiles of SEL_TILE rows.
-__global__ __launch_bounds__(SB) void k_sel_gather(SelBufs f) {
+// (amdgpu_waves_per_eu: the width-2 case must not cost the other widths a wave per SIMD; 80 VGPRs, no scratch)
+__global__ __launch_bounds__(SB) __attribute__((amdgpu_waves_per_eu(6))) void k_sel_gather(SelBufs f) {
     const DevSelChunk c = f.sc[blockIdx.y];
     if (c.status != 0) return;
     const int64_t nsel = f.head->rows_selected, ntiles = tiles_of(nsel);
@@ -424,14 +424,16 @@ __global__ __launch_bounds__(SB) void k_sel_fin(SelBufs f) {
 
 }  // namespace
 
-void launch_filter(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWinRes* d_wres, const SelBufs& f, int n_chunks,
-                   int gather_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
-                   hipStream_t st) {
+void launch_filter(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWinRes* d_wres, const SelBufs& f,
+                   const SelDictBufs& fd, int n_chunks, int gather_grid, const uint8_t* chars_base, uint8_t* wchars_base,
+                   int64_t out_delta, int64_t bits_delta, hipStream_t st) {
     if (f.n_preds <= 0 || n_chunks <= 0) return;
     const dim3 tiles(unsigned(f.tiles_cap < 1 ? 1 : f.tiles_cap)), per_chunk(unsigned(gather_grid < 1 ? 1 : gather_grid), unsigned(n_chunks));
     hipLaunchKernelGGL(k_sel_prep, dim3(1), dim3(SB), 0, st, d_chunks, d_res, d_wres, f, n_chunks, chars_base, wchars_base, out_delta,
-                       bits_delta);
-    hipLaunchKernelGGL(k_sel_mask, tiles, dim3(SB), 0, st, f);
+                       bits_delta, fd.keep_of, fd.keeps);
+    // predicates on kept chunks: matched once per dictionary entry, then looked up per row (pf_filter_dict.hip)
+    if (fd.n_recs > 0) launch_sel_dict(f, fd, tiles.x, st);
+    else hipLaunchKernelGGL(k_sel_mask, tiles, dim3(SB), 0, st, f);
     hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(SB), 0, st, f.tile_count, f.tile_base, int64_t(0), f.head, 0,
                        static_cast<const DevSelChunk*>(nullptr), &f.head->rows_selected);
     hipLaunchKernelGGL(k_sel_rows, tiles, dim3(SB), 0, st, f);

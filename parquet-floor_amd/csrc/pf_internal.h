@@ -388,6 +388,28 @@ struct SelBufs {
     int32_t n_preds;
 };
 
+// Predicates over kept dictionaries (pf_filter_dict.hip, pf_decode_row_group_dict_filter): a PF_PRED_RANGE on a kept
+// chunk is evaluated once per dictionary entry into a match bitmap (k_sel_dict) and looked up per row through the
+// chunk's indices (k_sel_mask_dict). One DevSelDict per such predicate, in a table of its own behind the filter
+// stage's other tables, so DevPred and SelBufs are what they are for a batch without one.
+constexpr uint32_t SELD_TILE = 256;          // dictionary entries per workgroup of k_sel_dict: four bitmap words
+struct DevSelDict {
+    int32_t pred;             // the predicate's entry in SelBufs.preds
+    int32_t keep;             // its chunk's entry in the DevKeep table
+    int64_t n_entries;        // the dictionary page's num_values
+    uint64_t word_off;        // first word of its bitmap in SelDictBufs.bits
+    uint64_t n_words;         // ceil(n_entries / 64)
+};
+struct SelDictBufs {
+    const DevSelDict* recs;   // [n_recs]
+    const int32_t* dict_of;   // [n_preds]: the predicate's entry in recs, -1: evaluated row by row
+    uint64_t* bits;           // the match bitmaps, back to back
+    const DevKeep* keeps;     // the batch's kept-dictionary tables (metadata block)
+    const int32_t* keep_of;
+    int32_t n_recs;
+    int32_t tiles;            // SELD_TILE tiles of the largest dictionary, at least one
+};
+
 // GPU page-header scan (pf_scan.hip, pf_scan_pages)
 struct ScanChunk {            // device copy of pf_scan_chunk
     const uint8_t* base;      // chunk's first byte

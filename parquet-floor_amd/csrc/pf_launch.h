@@ -86,12 +86,16 @@ void launch_dba_chars(const DevChunk* d_chunks, DevPage* d_pages, const int* d_l
 // pf_window.hip: out_delta / bits_delta = twin arena base - decode arena base (bytes)
 void launch_window(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWin* d_wins, DevWinRes* d_wres, int n_wins,
                    int copy_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
-                   hipStream_t st);
+                   const int* d_keep_of, const DevKeep* d_keeps, hipStream_t st);   // (the kept-dictionary tables, or null)
 
-// pf_filter.hip: the filter stage's launch (SelBufs: pf_internal.h, laid out and bound by pf_result.cpp)
-void launch_filter(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWinRes* d_wres, const SelBufs& f, int n_chunks,
-                   int gather_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
-                   hipStream_t st);
+// pf_filter.hip: the filter stage's launch (SelBufs, SelDictBufs: pf_internal.h, laid out and bound by pf_result.cpp)
+void launch_filter(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWinRes* d_wres, const SelBufs& f,
+                   const SelDictBufs& fd, int n_chunks, int gather_grid, const uint8_t* chars_base, uint8_t* wchars_base,
+                   int64_t out_delta, int64_t bits_delta, hipStream_t st);
+
+// pf_filter_dict.hip: k_sel_dict and the mask pass that reads its bitmaps (called by launch_filter in place of k_sel_mask
+// when a predicate is on a kept chunk)
+void launch_sel_dict(const SelBufs& f, const SelDictBufs& fd, unsigned row_tiles, hipStream_t st);
 
 // pf_scan.hip
 void launch_page_scan(const ScanChunk* d_chunks, int n_chunks, pf_page_desc* d_pages, ScanCrc* d_crcs, ScanResult* d_res,

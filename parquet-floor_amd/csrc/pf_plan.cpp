@@ -634,11 +634,17 @@ void bind_batch(BatchPlan& p, const ArenaBases& a) {
 int plan_filter(const pf_chunk_desc* cds, int n_chunks, const pf_predicate* preds, int n_preds, FilterPlan& f, const char** why) {
     const char* dummy;
     if (!why) why = &dummy;
-    f.preds.clear();
-    f.blob.clear();
-    auto bad = [&](int code, const char* text) {
+    auto reset = [&]() {
         f.preds.clear();
         f.blob.clear();
+        f.dicts.clear();
+        f.dict_of.clear();
+        f.dict_words = 0;
+        f.dict_max_entries = 0;
+    };
+    reset();
+    auto bad = [&](int code, const char* text) {
+        reset();
         *why = text;
         return code;
     };
@@ -700,6 +706,30 @@ int plan_filter(const pf_chunk_desc* cds, int n_chunks, const pf_predicate* pred
     }
     *why = "";
     return PF_OK;
+}
+
+void plan_filter_dict(const BatchPlan& p, FilterPlan& f) {
+    f.dicts.clear();
+    f.dict_of.clear();
+    f.dict_words = 0;
+    f.dict_max_entries = 0;
+    if (p.keeps.empty()) return;
+    for (size_t i = 0; i < f.preds.size(); i++) {
+        const DevPred& d = f.preds[i];
+        const int32_t k = d.op == PF_PRED_RANGE && size_t(d.chunk) < p.keep_of.size() ? p.keep_of[size_t(d.chunk)] : -1;
+        if (k < 0) continue;
+        if (f.dict_of.empty()) f.dict_of.assign(f.preds.size(), -1);
+        DevSelDict r{};
+        r.pred = int32_t(i);
+        r.keep = k;
+        r.n_entries = std::max<int64_t>(p.keeps[size_t(k)].n_entries, 0);
+        r.word_off = f.dict_words;
+        r.n_words = (uint64_t(r.n_entries) + 63) / 64;
+        f.dict_words += r.n_words;
+        f.dict_max_entries = std::max(f.dict_max_entries, r.n_entries);
+        f.dict_of[i] = int32_t(f.dicts.size());
+        f.dicts.push_back(r);
+    }
 }
 
 }  // namespace pf

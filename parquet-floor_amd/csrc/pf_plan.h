@@ -146,11 +146,21 @@ void bind_batch(BatchPlan& p, const ArenaBases& a);
 
 // The predicates of a filtered decode, validated and packed for the device: the DevPred table and, behind it, the
 // blob that holds the BYTE_ARRAY bounds (DevPred.lo_off / hi_off). Reads the descriptors and the bounds, nothing else.
+// dicts / dict_of / dict_words (plan_filter_dict): the PF_PRED_RANGE predicates on kept chunks, each with a match bitmap
+// over its dictionary's entries; all empty / 0 for a batch without one, whose filter stage is then what it always was.
 struct FilterPlan {
     std::vector<DevPred> preds;
     std::vector<uint8_t> blob;
+    std::vector<DevSelDict> dicts;
+    std::vector<int32_t> dict_of;          // per predicate: its entry in dicts, -1; empty when dicts is
+    uint64_t dict_words = 0;               // 64-bit words of all bitmaps
+    int64_t dict_max_entries = 0;          // entries of the largest dictionary among dicts
 };
 // PF_OK, or the call error of pf_decode_row_group_filter with its text in *why (f is then empty).
 int plan_filter(const pf_chunk_desc* cds, int n_chunks, const pf_predicate* preds, int n_preds, FilterPlan& f, const char** why);
+// After plan_batch: which of f's predicates are resolved through a kept dictionary (p.keep_of), and where their bitmaps
+// of ceil(n_entries / 64) words lie, back to back in predicate order. IS_NULL / NOT_NULL read the validity only and get
+// none. Reads the plan, nothing else.
+void plan_filter_dict(const BatchPlan& p, FilterPlan& f);
 
 }  // namespace pf

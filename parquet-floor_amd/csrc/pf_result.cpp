@@ -59,6 +59,11 @@ SelLayout layout_filter(const BatchPlan& p, const FilterPlan& f, const std::vect
     l.o_preds = take(sizeof(DevPred) * np);
     l.o_blob = take(f.blob.size());
     l.o_winof = take(4 * nc);
+    const size_t nd = f.dicts.size();
+    if (nd > 0) {   // (behind the existing tables, and only then: a batch without one keeps its layout)
+        l.o_drec = take(sizeof(DevSelDict) * nd);
+        l.o_dof = take(4 * np);
+    }
     l.up_end = m;
     l.o_mask = take(8 * tiles * (SEL_TILE / 64));
     l.o_tc = take(4 * tiles);
@@ -67,6 +72,10 @@ SelLayout layout_filter(const BatchPlan& p, const FilterPlan& f, const std::vect
     l.o_bs = take(4 * tiles * nc);
     l.o_bb = take(4 * tiles * nc);
     l.o_bt = take(8 * nc);
+    if (nd > 0) {
+        l.o_dbits = take(8 * size_t(f.dict_words));
+        l.dict_tiles = int(std::max<int64_t>(1, (f.dict_max_entries + SELD_TILE - 1) / SELD_TILE));
+    }
     l.total = m;
     return l;
 }
@@ -76,6 +85,10 @@ void fill_filter(const SelLayout& l, const FilterPlan& f, uint8_t* h) {
     std::memcpy(h + l.o_preds, f.preds.data(), sizeof(DevPred) * f.preds.size());
     if (!f.blob.empty()) std::memcpy(h + l.o_blob, f.blob.data(), f.blob.size());
     if (!l.win_of.empty()) std::memcpy(h + l.o_winof, l.win_of.data(), 4 * l.win_of.size());
+    if (!f.dicts.empty()) {
+        std::memcpy(h + l.o_drec, f.dicts.data(), sizeof(DevSelDict) * f.dicts.size());
+        std::memcpy(h + l.o_dof, f.dict_of.data(), 4 * f.dict_of.size());
+    }
 }
 
 SelBufs bind_sel(const SelLayout& l, const FilterPlan& f, uintptr_t base) {
@@ -96,6 +109,20 @@ SelBufs bind_sel(const SelLayout& l, const FilterPlan& f, uintptr_t base) {
     s.rows_cap = l.rows_cap;
     s.tiles_cap = int64_t(l.tiles);
     s.n_preds = int32_t(f.preds.size());
+    return s;
+}
+
+SelDictBufs bind_sel_dict(const SelLayout& l, const FilterPlan& f, uintptr_t base, const DevKeep* keeps, const int32_t* keep_of) {
+    SelDictBufs s{};
+    s.keeps = keeps;   // (k_sel_prep sizes a kept payload chunk by them, whatever the predicates are on)
+    s.keep_of = keep_of;
+    if (f.dicts.empty()) return s;
+    uint8_t* d = reinterpret_cast<uint8_t*>(base);
+    s.recs = reinterpret_cast<const DevSelDict*>(d + l.o_drec);
+    s.dict_of = reinterpret_cast<const int32_t*>(d + l.o_dof);
+    s.bits = reinterpret_cast<uint64_t*>(d + l.o_dbits);
+    s.n_recs = int32_t(f.dicts.size());
+    s.tiles = l.dict_tiles;
     return s;
 }
 
@@ -144,7 +171,9 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
     for (int c = 0; c < p.n_chunks; c++) {
         pf_column_info& ci = info[c];
         const DevChunk& ck = p.chunks[size_t(c)];
-        const bool ba = ck.ptype == PF_BYTE_ARRAY;
+        const int32_t k = p.keep_of.empty() ? -1 : p.keep_of[size_t(c)];
+        // (a kept chunk is a fixed-width column of index_width bytes in every view: no offsets, no chars)
+        const bool ba = ck.ptype == PF_BYTE_ARRAY && k < 0;
         ci.num_entries = ck.num_entries;
         ci.num_slots = r[c].num_slots;
         ci.num_values = r[c].num_values;
@@ -161,7 +190,6 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
         ci.d_def_levels = ck.def_levels;
         ci.d_rep_levels = ck.rep_levels;
         if (dinfo) dinfo[c] = pf_dict_info{};
-        const int32_t k = p.keep_of.empty() ? -1 : p.keep_of[size_t(c)];
         if (k >= 0) {   // kept dictionary: `values` are indices; the dictionary has the chars
             const KeepPlan& kp = p.keeps[size_t(k)];
             ci.width = kp.index_width;
@@ -196,8 +224,8 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
                 ci.num_chars = ba ? w.n_chars : 0;
                 ci.d_values = shifted(ck.values, od);
                 ci.d_validity = shifted(ck.validity, bd);
-                ci.d_offsets = shifted(ck.offsets, od);
-                ci.d_chars = w.chars_dst;
+                ci.d_offsets = k < 0 ? shifted(ck.offsets, od) : nullptr;
+                ci.d_chars = k < 0 ? w.chars_dst : nullptr;
                 ci.d_list_offsets = shifted(ck.list_offsets, od);
                 ci.d_list_validity = shifted(ck.list_validity, bd);
                 ci.d_def_levels = shifted(ck.def_levels, od);
@@ -213,8 +241,8 @@ FirstError assemble_info(const BatchPlan& p, const BatchResults& in, pf_column_i
                 ci.num_chars = ba ? sc.n_chars : 0;
                 ci.d_values = sc.o_values;
                 ci.d_validity = sc.o_validity;
-                ci.d_offsets = sc.o_offsets;
-                ci.d_chars = sc.o_chars;
+                ci.d_offsets = k < 0 ? sc.o_offsets : nullptr;
+                ci.d_chars = k < 0 ? sc.o_chars : nullptr;
             }
         }
         if (ci.status != 0 && err.code == PF_OK) {

@@ -43,6 +43,11 @@ struct TwinDelta {
 struct SelLayout {
     size_t o_head = 0, o_sc = 0, o_up = 0, o_preds = 0, o_blob = 0, o_winof = 0, up_end = 0;
     size_t o_mask = 0, o_tc = 0, o_tb = 0, o_rows = 0, o_bs = 0, o_bb = 0, o_bt = 0, total = 0;
+    // predicates resolved through kept dictionaries (FilterPlan.dicts; none: every field is 0 and the fields above are
+    // what they are without): [DevSelDict[] | dict_of[n_preds]] behind win_of in the uploaded part, the match bitmaps
+    // (dict_words 64-bit words) behind ba_total
+    size_t o_drec = 0, o_dof = 0, o_dbits = 0;
+    int dict_tiles = 0;              // k_sel_dict's grid.x: SELD_TILE tiles of the largest dictionary, at least one
     int64_t rows_cap = 0;            // bounds rows_in: the first predicate chunk's rows after its window
     size_t tiles = 1;                // SEL_TILE tiles of rows_cap, at least one
     int grid = 1;                    // the gather kernels' workgroups: min(tiles, 256)
@@ -53,6 +58,9 @@ SelLayout layout_filter(const BatchPlan& p, const FilterPlan& f, const std::vect
 void fill_filter(const SelLayout& l, const FilterPlan& f, uint8_t* h);
 // The stage's pointers for a buffer at `base`.
 SelBufs bind_sel(const SelLayout& l, const FilterPlan& f, uintptr_t base);
+// The dictionary route's pointers (n_recs = 0 and no tables without FilterPlan.dicts); keeps / keep_of: the batch's
+// DevKeep[] and keep_of[] on the device (null: nothing kept), passed on as they are.
+SelDictBufs bind_sel_dict(const SelLayout& l, const FilterPlan& f, uintptr_t base, const DevKeep* keeps, const int32_t* keep_of);
 
 // Arena capacities a batch asks for (out: before the "at least one byte" of its allocation).
 struct ArenaNeeds {

@@ -209,13 +209,14 @@ int enqueue_kernels(pf_ctx* ctx) {
         EVREC(ctx, ctx->ev_win[0], st);
         launch_window(d_chunks, d_res, static_cast<DevWin*>(ctx->d_win.p), d_wres, int(ctx->wins.size()), ctx->win_grid,
                       static_cast<const uint8_t*>(ctx->d_chars.p), static_cast<uint8_t*>(ctx->d_wchars.p), ctx->twin.out,
-                      ctx->twin.bits, st);
+                      ctx->twin.bits, n_keeps > 0 ? reinterpret_cast<const int*>(meta + p.off_keepof) : nullptr,
+                      n_keeps > 0 ? reinterpret_cast<const DevKeep*>(meta + p.off_keeps) : nullptr, st);
         EVREC(ctx, ctx->ev_win[1], st);
         HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->h_win.p) + wl.res_off, d_wres, wl.res_bytes, hipMemcpyDeviceToHost, st));
     }
     if (ctx->filtered()) {   // the row filter: after the windows, so it sees their rows and a chars rerun filters again
         EVREC(ctx, ctx->ev_sel[0], st);
-        launch_filter(d_chunks, d_res, d_wres, ctx->sel, ctx->n_chunks, ctx->sel_lay.grid, static_cast<const uint8_t*>(ctx->d_chars.p),
+        launch_filter(d_chunks, d_res, d_wres, ctx->sel, ctx->sel_dict, ctx->n_chunks, ctx->sel_lay.grid, static_cast<const uint8_t*>(ctx->d_chars.p),
                       static_cast<uint8_t*>(ctx->d_wchars.p), ctx->twin.out, ctx->twin.bits, st);
         EVREC(ctx, ctx->ev_sel[1], st);
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_sel.p, ctx->d_sel.p, ctx->sel_lay.o_up, hipMemcpyDeviceToHost, st));
@@ -511,6 +512,7 @@ int bind_filter(pf_ctx* ctx) {
     HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->d_sel.p) + l.o_up, h + l.o_up, l.up_end - l.o_up, hipMemcpyHostToDevice,
                                ctx->stream));
     ctx->sel = bind_sel(l, ctx->filt, reinterpret_cast<uintptr_t>(ctx->d_sel.p));
+    ctx->sel_dict = SelDictBufs{};   // (its metadata pointers: enqueue_batch, once d_meta is sized)
     return PF_OK;
 }
 
@@ -577,11 +579,18 @@ int enqueue_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uin
         ctx->win_grid = win_grid(p, ctx->wins);
     }
     if (ctx->filtered()) {
+        plan_filter_dict(p, ctx->filt);   // which predicates are on chunks the plan keeps
         const int rc = bind_filter(ctx);
         if (rc) return rc;
     }
     HIPCHK(ctx, ctx->d_tokmap.ensure(p.snap.tokmap_bytes));
     HIPCHK(ctx, ctx->d_meta.ensure(p.meta_bytes));
+    if (ctx->filtered() && !p.keeps.empty()) {
+        const uint8_t* meta = static_cast<const uint8_t*>(ctx->d_meta.p);
+        ctx->sel_dict = bind_sel_dict(ctx->sel_lay, ctx->filt, reinterpret_cast<uintptr_t>(ctx->d_sel.p),
+                                      reinterpret_cast<const DevKeep*>(meta + p.off_keeps),
+                                      reinterpret_cast<const int32_t*>(meta + p.off_keepof));
+    }
     HIPCHK(ctx, ctx->h_meta.ensure(p.meta_bytes));
     ctx->res_lay = res_layout(n_chunks);
     HIPCHK(ctx, ctx->h_res.ensure(ctx->res_lay.total));
@@ -623,6 +632,8 @@ int decode_batch(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_r
     ctx->wins.clear();
     ctx->filt.preds.clear();
     ctx->filt.blob.clear();
+    ctx->filt.dicts.clear();
+    ctx->filt.dict_of.clear();
     if (n_preds != 0) {   // (a predicate error leaves the lists cleared, like an enqueue error below)
         const char* why = "";
         const int rc = plan_filter(cds, n_chunks, preds, n_preds, ctx->filt, &why);
@@ -651,6 +662,12 @@ int pf_decode_row_group(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, con
 int pf_decode_row_group_dict(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* keep, const uint8_t* bytes,
                              size_t n_bytes, int bytes_on_device) {
     return decode_batch(ctx, cds, n_chunks, nullptr, nullptr, 0, bytes, n_bytes, bytes_on_device, keep);
+}
+
+int pf_decode_row_group_dict_filter(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const uint8_t* keep,
+                                    const pf_row_window* windows, const pf_predicate* preds, int n_preds, const uint8_t* bytes,
+                                    size_t n_bytes, int bytes_on_device) {
+    return decode_batch(ctx, cds, n_chunks, windows, preds, n_preds, bytes, n_bytes, bytes_on_device, keep);
 }
 
 int pf_decode_row_group_rows(pf_ctx* ctx, const pf_chunk_desc* cds, int n_chunks, const pf_row_window* windows,

@@ -239,12 +239,17 @@ __device__ __forceinline__ T* twin(const T* p, int64_t delta) {
 // Grid (tiles, windowed chunk). A chunk's arrays are laid end to end in tiles of WIN_TILE output bytes; the workgroups
 // of its row stride over them (the sizes are known only on the device, so the host sizes the grid from capacities).
 __global__ __launch_bounds__(WB) void k_win_copy(const DevChunk* __restrict__ chunks, const DevWin* __restrict__ wins,
-                                                 const DevWinRes* __restrict__ wres, int64_t out_delta, int64_t bits_delta) {
+                                                 const DevWinRes* __restrict__ wres, int64_t out_delta, int64_t bits_delta,
+                                                 const int32_t* __restrict__ keep_of, const DevKeep* __restrict__ keeps) {
     const DevWinRes r = wres[blockIdx.y];
     if (r.status != 0 || r.identity) return;
     const DevChunk& ck = chunks[wins[blockIdx.y].chunk];
     const int64_t skip = wins[blockIdx.y].skip;
-    const int64_t nb_val = ck.values && ck.width > 0 ? r.n_slots * ck.width : 0;
+    // a kept chunk's values are its indices, index_width bytes a slot (ck.width is its dictionary's entry width); it
+    // has no offsets and no chars, and its dictionary stays where it is
+    const int32_t kp = keep_of ? keep_of[wins[blockIdx.y].chunk] : -1;
+    const int64_t width = kp >= 0 ? keeps[kp].index_width : ck.width;
+    const int64_t nb_val = ck.values && width > 0 ? r.n_slots * width : 0;
     const int64_t nb_def = ck.def_levels ? r.n_entries : 0, nb_rep = ck.rep_levels ? r.n_entries : 0;
     const int64_t nb_chr = r.chars_src ? r.n_chars : 0;
     const int64_t nb_off = ck.offsets ? 4 * (r.n_slots + 1) : 0, nb_lof = ck.list_offsets ? 4 * (r.n_rows + 1) : 0;
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(WB) void k_win_copy(const DevChunk* __restrict__ ch
     const int64_t t0 = tiles_of(nb_val), t1 = t0 + tiles_of(nb_def), t2 = t1 + tiles_of(nb_rep), t3 = t2 + tiles_of(nb_chr),
                   t4 = t3 + tiles_of(nb_off), t5 = t4 + tiles_of(nb_lof), t6 = t5 + tiles_of(nb_vld), t7 = t6 + tiles_of(nb_lvl);
     for (int64_t g = blockIdx.x; g < t7; g += gridDim.x) {
-        if (g < t0) copy_tile(twin(ck.values, out_delta), ck.values + r.s0 * ck.width, nb_val, g);
+        if (g < t0) copy_tile(twin(ck.values, out_delta), ck.values + r.s0 * width, nb_val, g);
         else if (g < t1) copy_tile(twin(ck.def_levels, out_delta), ck.def_levels + r.e0, nb_def, g - t0);
         else if (g < t2) copy_tile(twin(ck.rep_levels, out_delta), ck.rep_levels + r.e0, nb_rep, g - t1);
         else if (g < t3) copy_tile(r.chars_dst, r.chars_src + r.c0, nb_chr, g - t2);
@@ -267,11 +272,11 @@ __global__ __launch_bounds__(WB) void k_win_copy(const DevChunk* __restrict__ ch
 
 void launch_window(const DevChunk* d_chunks, const DevChunkResult* d_res, const DevWin* d_wins, DevWinRes* d_wres, int n_wins,
                    int copy_grid, const uint8_t* chars_base, uint8_t* wchars_base, int64_t out_delta, int64_t bits_delta,
-                   hipStream_t st) {
+                   const int* d_keep_of, const DevKeep* d_keeps, hipStream_t st) {
     if (n_wins <= 0) return;
     hipLaunchKernelGGL(k_win_bounds, dim3(n_wins), dim3(WB), 0, st, d_chunks, d_res, d_wins, d_wres, chars_base, wchars_base);
     hipLaunchKernelGGL(k_win_copy, dim3(copy_grid < 1 ? 1 : copy_grid, n_wins), dim3(WB), 0, st, d_chunks, d_wins, d_wres,
-                       out_delta, bits_delta);
+                       out_delta, bits_delta, d_keep_of, d_keeps);
 }
 
 }  // namespace pf

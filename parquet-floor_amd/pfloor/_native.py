@@ -169,6 +169,8 @@ def _load(path):
         "pf_decode_row_group": ([vp, C.POINTER(ChunkDesc), i32, vp, sz, i32], C.c_int),
         "pf_decode_row_group_rows": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(RowWindow), vp, sz, i32], C.c_int),
         "pf_decode_row_group_dict": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(C.c_uint8), vp, sz, i32], C.c_int),
+        "pf_decode_row_group_dict_filter": ([vp, C.POINTER(ChunkDesc), i32, C.POINTER(C.c_uint8), C.POINTER(RowWindow),
+                                             C.POINTER(Predicate), i32, vp, sz, i32], C.c_int),
         "pf_dict_info_get": ([vp, i32, C.POINTER(DictInfo)], C.c_int),
         "pf_dict_info_host": ([vp, i32, vp, C.POINTER(DictInfo)], C.c_int),
         "pf_copy_dictionary": ([vp, i32, C.POINTER(ColumnOut)], C.c_int),

@@ -361,6 +361,22 @@ class PinnedBuffer:
             pass
 
 
+def _pack_predicates(predicates):
+    """[(chunk, op, lo, hi)] as a ctypes Predicate array, and the bounds' buffers, which must stay alive over the call
+    (the library copies them before it returns)."""
+    preds = (Predicate * max(1, len(predicates)))()
+    alive = []
+    for i, (chunk, op, lo, hi) in enumerate(predicates):
+        preds[i].chunk, preds[i].op = int(chunk), int(op)
+        for side, b in (("lo", lo), ("hi", hi)):
+            if b is not None:
+                raw = C.create_string_buffer(bytes(b), max(1, len(b)))
+                alive.append(raw)
+                setattr(preds[i], side, C.addressof(raw))
+                setattr(preds[i], side + "_len", len(b))
+    return preds, alive
+
+
 class GpuDecoder:
     """One pf_ctx = one GPU + one HIP stream."""
 
@@ -422,16 +438,7 @@ class GpuDecoder:
             if windows is not None and len(windows) != len(descs):
                 raise ValueError("one window per chunk")
             win = None if windows is None else (RowWindow * max(1, len(windows)))(*[RowWindow(int(s), int(t)) for s, t in windows])
-            preds = (Predicate * max(1, len(predicates)))()
-            keep = []   # the bounds' buffers, alive over the call (the library copies them before it returns)
-            for i, (chunk, op, lo, hi) in enumerate(predicates):
-                preds[i].chunk, preds[i].op = int(chunk), int(op)
-                for side, b in (("lo", lo), ("hi", hi)):
-                    if b is not None:
-                        raw = C.create_string_buffer(bytes(b), max(1, len(b)))
-                        keep.append(raw)
-                        setattr(preds[i], side, C.addressof(raw))
-                        setattr(preds[i], side + "_len", len(b))
+            preds, _alive = _pack_predicates(predicates)
             check(lib().pf_decode_row_group_filter(self.h, arr, len(descs), win, preds, len(predicates), C.c_void_p(buf_ptr), nbytes,
                                                    1 if on_device else 0), self.h, "pf_decode_row_group_filter")
         elif windows is None:
@@ -444,6 +451,26 @@ class GpuDecoder:
             check(lib().pf_decode_row_group_rows(self.h, arr, len(descs), win, C.c_void_p(buf_ptr), nbytes,
                                                  1 if on_device else 0), self.h, "pf_decode_row_group_rows")
         self.n_chunks = len(descs)
+
+    def decode_kept(self, descs, buf_ptr, nbytes, on_device=False, keep=None, windows=None, predicates=None):
+        """decode() with keep flags that go together with windows and predicates (pf_decode_row_group_dict_filter): a
+        chunk that is dictionary-encoded throughout comes back as the indices of the window's / the selection's rows +
+        its whole dictionary (fetch, materialize); a predicate on such a chunk is matched once per dictionary entry.
+        keep=None: decode(windows=, predicates=); no windows and no predicates: decode(keep=). info, dict_info, fetch,
+        selection and materialize work on the result; fetch_batch only after a decode without windows and predicates."""
+        n = len(descs)
+        for name, v in (("keep flag", keep), ("window", windows)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"one {name} per chunk")
+        arr = descs if isinstance(descs, C.Array) else (ChunkDesc * max(1, n))(*descs)
+        self._keep = arr
+        flags = None if keep is None else (C.c_uint8 * max(1, n))(*[1 if k else 0 for k in keep])
+        win = None if windows is None else (RowWindow * max(1, n))(*[RowWindow(int(s), int(t)) for s, t in windows])
+        preds, _alive = _pack_predicates(predicates or [])
+        check(lib().pf_decode_row_group_dict_filter(self.h, arr, n, flags, win, preds if predicates else None, len(predicates or []),
+                                                    C.c_void_p(buf_ptr), nbytes, 1 if on_device else 0), self.h,
+              "pf_decode_row_group_dict_filter")
+        self.n_chunks = n
 
     def selection(self):
         """(rows_in, the selected row numbers as np.int32, ascending, counted from the window's first row) of the last
@@ -760,10 +787,9 @@ def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, row
     hold the matching rows only. "_selection" = (rows_in, row numbers within the row group as np.int64), "_range" =
     the rows that were decoded, None when the row group was skipped (no chunk is returned then). A predicate column
     outside `columns` is decoded and not returned.
-    dictionaries=True (whole-file decodes only): every chunk that is dictionary-encoded throughout comes back as
-    "indices" + "dictionary" (GpuDecoder.decode(keep=...)); materialize() expands one on the host."""
-    if dictionaries and (rows is not None or where is not None):
-        raise ValueError("dictionaries=True reads whole row groups: no rows= and no where=")
+    dictionaries=True: every chunk that is dictionary-encoded throughout comes back as "indices" + "dictionary"
+    (GpuDecoder.decode(keep=...); with rows= or where=, GpuDecoder.decode_kept: the indices of the window's or the
+    selection's rows and the whole dictionary); materialize() expands one on the host."""
     with ParquetFile(path) as pf:
         rgs = list(range(pf.num_row_groups)) if row_groups is None else list(row_groups)
         cols = list(range(pf.num_columns)) if columns is None else list(columns)
@@ -787,7 +813,11 @@ def decode_file(path, row_groups=None, columns=None, device=0, decoder=None, row
                 buf = dec.staging(total)
                 pf.read_rows(items, buf.ptr.value)
                 extra = {} if preds is None else {"predicates": preds}
-                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=windows, **extra)
+                descs = [d for _c, d, _r, _o in items]
+                if dictionaries:
+                    dec.decode_kept(descs, buf.ptr.value, max(total, 1), keep=[True] * len(descs), windows=windows, **extra)
+                else:
+                    dec.decode(descs, buf.ptr.value, max(total, 1), windows=windows, **extra)
                 rc = dec.wait()
                 out = {}
                 for i, col in enumerate(cols):

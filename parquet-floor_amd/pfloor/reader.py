@@ -263,7 +263,7 @@ class RowGroupPipeline:
     `selections[i]` = (rows_in, rows_selected) of row_groups[i] once taken; `bytes_read` counts the chunk bytes read."""
 
     def __init__(self, reader, columns, row_groups, devices=(0,), depth=2, windows=None, where=None, dictionaries=False):
-        self.dictionaries = bool(dictionaries)   # row groups read whole keep their eligible chunks' dictionaries
+        self.dictionaries = bool(dictionaries)   # every row group keeps its eligible chunks' dictionaries
         if not devices:
             raise ValueError("devices must not be empty")
         self.reader = reader
@@ -312,7 +312,11 @@ class RowGroupPipeline:
                 buf = dec.staging(total)
                 self.bytes_read += self.reader.read_rows(items, buf.ptr.value)
                 extra = {} if self._preds is None else {"predicates": self._preds}
-                dec.decode([d for _c, d, _r, _o in items], buf.ptr.value, max(total, 1), windows=wins, **extra)
+                descs = [d for _c, d, _r, _o in items]
+                if self.dictionaries:   # windowed and filtered row groups keep their dictionaries too
+                    dec.decode_kept(descs, buf.ptr.value, max(total, 1), keep=[True] * len(descs), windows=wins, **extra)
+                else:
+                    dec.decode(descs, buf.ptr.value, max(total, 1), windows=wins, **extra)
                 self.inflight[i] = dec
                 return
             items, total = self.reader.plan([rg], idx)
@@ -375,7 +379,7 @@ class ParquetReader:
         the rest are read by page over what remains, filtered on the GPU and compacted there, so only matching rows
         cross the link. A predicate column outside `columns` is decoded and never passed to the Hydrator. A projected
         or predicate column with repetition is an IllegalArgumentException. `filter_stats` counts what happened.
-        dictionaries=True: a row group that is read whole (no rows= edge, no where=) keeps the dictionary of every chunk
+        dictionaries=True: every row group, windowed and filtered ones included, keeps the dictionary of every chunk
         that is dictionary-encoded throughout: indices and dictionary cross the link instead of expanded values, and
         each dictionary entry is converted once per row group. Rows, call order and exceptions are those of the default."""
         column_set = frozenset() if columns is None else frozenset(columns)
