@@ -11,13 +11,19 @@
 // (pf_flat_count.hip: k_runs, k_count_dict, k_count_flat), then the levels of nullable pages
 // (pf_flat_null.hip: k_lvl), then the flat stage, which launch_flat puts on the stream in this order:
 //   k_flat_null<4|8>  (pf_flat_null.hip) per (page, block) with nulls, fixed width
-//   k_flat_fixed   per (page, block), fixed width, all present
+//   k_flat_fixed   per (page, block), fixed width, all present; dictionary pages with a whole-page run table
+//                  eight consecutive ids a thread (flat_fixed8, pf_fix_ids.h)
 //   k_flat_dstr    (pf_flat_dstr.hip) per (page, block) of dictionary BYTE_ARRAY pages with a small
 //                  dictionary of short values, all present
 //   k_flat_all     per (page, block): every other flat page (BYTE_ARRAY, booleans, ...), and the
 //                  fallback queue of blocks k_flat_null and k_flat_fixed did not take
 #include <hip/hip_runtime.h>
 
+#ifdef PF_DIAG
+#include <cstdlib>   // getenv (PF_FIX8: diagnostics build only)
+#endif
+
+#include "pf_fix_ids.h"
 #include "pf_flat.h"
 #include "pf_flat_chars.h"
 #include "pf_launch.h"
@@ -305,10 +311,234 @@ __device__ __forceinline__ int flat_present_fixed(Lds& S, const DevChunk& ck, co
     return 0;
 }
 
+// ---- k_flat_fixed's body for dictionary pages with a whole-page run table: eight ids a thread ----
+// Thread t owns the 8-entry groups t + NT * k of the block (blocks start at multiples of FBLK, so groups are aligned
+// from the page's entry 0). A group inside one run is one run lookup and one contiguous load of its id bytes
+// (pf_fix_ids.h); the loads of FIX_GR groups a thread are issued together, the dictionary is staged behind them, and
+// after the one barrier the ids are unpacked with constant shifts, gathered (LDS, or eight global loads in flight)
+// and stored 16 bytes at a time. A group that straddles runs, the block's last partial group in a packed run, or a
+// group whose words would reach outside the id section is decoded entry by entry as flat_present_fixed does.
+#ifdef PF_DIAG   // diagnostics build: blocks this body decoded, groups it decoded entry by entry, blocks of dictionary
+                 // pages k_flat_fixed gave to flat_present_fixed (tests)
+__device__ unsigned long long pf_fix8_counts[3];
+extern "C" int pf_debug_fix8_counts(unsigned long long* out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pf_fix8_counts), sizeof(unsigned long long) * 3) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long z[3] = {0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(pf_fix8_counts), z, sizeof z) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#define FIX8_COUNT(i, n) ((void)atomicAdd(&pf_fix8_counts[i], (unsigned long long)(n)))
+#else
+#define FIX8_COUNT(i, n) ((void)0)
+#endif
+
+// bits_le (pf_device.h), spelled out: a call of it from this body changes k_flat_all's instruction text
+__device__ __forceinline__ uint32_t fix_bits_pad(const uint8_t* p, uint64_t n, uint64_t bit, int w) {
+    if (w == 0) return 0;
+    const uint64_t by = bit >> 3;
+    const int sh = int(bit & 7);
+    uint64_t acc = 0;
+    #pragma unroll
+    for (int k = 0; k < 5; k++)
+        if (8 * k < sh + w && by + k < n) acc |= uint64_t(p[by + k]) << (8 * k);
+    return uint32_t((acc >> sh) & (w == 32 ? 0xffffffffull : ((1ull << w) - 1)));
+}
+
+constexpr uint32_t FIX_GR = 4;   // groups a thread holds the id words of at a time (a block of 8192 entries: all of them)
+
+struct FixRowsLds {   // the block's run table (FixedLds::vrun) as pf_fix_ids.h reads rows
+    const Run* r;
+    __device__ __forceinline__ uint32_t first(uint32_t i) const { return r[i].first; }
+    __device__ __forceinline__ uint32_t end(uint32_t i) const { return r[i].first + r[i].count; }
+    __device__ __forceinline__ uint32_t packed(uint32_t i) const { return r[i].packed; }
+    __device__ __forceinline__ uint32_t data(uint32_t i) const { return r[i].data; }
+};
+struct FixMemGlobal {   // the frame of aligned words around a page's id section
+    const PF_GLOBAL uint8_t* base;
+    __device__ __forceinline__ uint32_t operator()(uint32_t o) const { return *reinterpret_cast<const PF_GLOBAL uint32_t*>(base + o); }
+};
+
+// A thread's 8 consecutive values at p (aligned to the value): LEAD single values up to the 16-byte boundary, then
+// 16-byte stores (store_offs16's pattern, pf_flat_dstr.hip).
+template <int LEAD>
+__device__ __forceinline__ void store_vals8(PF_GLOBAL uint32_t* p, const uint32_t (&v)[8]) {
+    #pragma unroll
+    for (int k = 0; k < LEAD; k++) p[k] = v[k];
+    #pragma unroll
+    for (int k = LEAD; k + 4 <= 8; k += 4) *reinterpret_cast<PF_GLOBAL u32x4*>(p + k) = u32x4{v[k], v[k + 1], v[k + 2], v[k + 3]};
+    #pragma unroll
+    for (int k = LEAD + (8 - LEAD) / 4 * 4; k < 8; k++) p[k] = v[k];
+}
+template <int LEAD>
+__device__ __forceinline__ void store_vals8(PF_GLOBAL uint64_t* p, const uint64_t (&v)[8]) {
+    #pragma unroll
+    for (int k = 0; k < LEAD; k++) p[k] = v[k];
+    #pragma unroll
+    for (int k = LEAD; k + 2 <= 8; k += 2)
+        *reinterpret_cast<PF_GLOBAL u32x4*>(p + k) = u32x4{uint32_t(v[k]), uint32_t(v[k] >> 32), uint32_t(v[k + 1]), uint32_t(v[k + 1] >> 32)};
+    #pragma unroll
+    for (int k = LEAD + (8 - LEAD) / 2 * 2; k < 8; k++) p[k] = v[k];
+}
+
+// The dictionary into LDS, eight loads a thread in flight per round (flat_present_fixed's loop)
+template <class V>
+__device__ __forceinline__ void fixed8_stage_dict(V* sd, const PF_GLOBAL V* gd, uint32_t dn) {
+    for (uint32_t i0 = threadIdx.x; i0 < dn; i0 += 8u * NT) {
+        V v[8];
+        #pragma unroll
+        for (uint32_t k = 0; k < 8; k++) v[k] = i0 + k * NT < dn ? gd[i0 + k * NT] : V(0);
+        #pragma unroll
+        for (uint32_t k = 0; k < 8; k++) if (i0 + k * NT < dn) sd[i0 + k * NT] = v[k];
+    }
+}
+
+// The eight values of ids id[0 .. 8) from the dictionary (sd: its LDS copy, or null: gd), n of them stored at p
+template <class V>
+__device__ __forceinline__ void fixed8_gather_store(const V* sd, const PF_GLOBAL V* gd, const uint32_t (&id)[8], PF_GLOBAL V* p,
+                                                    uint32_t n) {
+    V v[8];
+    if (sd != nullptr) {
+        #pragma unroll
+        for (uint32_t k = 0; k < 8; k++) v[k] = sd[id[k]];
+    } else {
+        #pragma unroll
+        for (uint32_t k = 0; k < 8; k++) v[k] = gd[id[k]];
+    }
+    if (n == 8) {
+        constexpr uint32_t per = 16u / sizeof(V);   // values per 16 bytes: 4 or 2
+        const uint32_t lead = (per - uint32_t((reinterpret_cast<uintptr_t>(p) / sizeof(V)) & (per - 1u))) & (per - 1u);
+        if constexpr (sizeof(V) == 4) {
+            switch (lead) {
+                case 0: store_vals8<0>(p, v); break;
+                case 1: store_vals8<1>(p, v); break;
+                case 2: store_vals8<2>(p, v); break;
+                default: store_vals8<3>(p, v); break;
+            }
+        } else {
+            if (lead == 0) store_vals8<0>(p, v);
+            else store_vals8<1>(p, v);
+        }
+    } else {
+        #pragma unroll
+        for (uint32_t k = 0; k < 8; k++) if (k < n) p[k] = v[k];
+    }
+}
+
+// w: 4 or 8. The run table covers the page (S.vrun, visible to all threads), the dictionary is aligned to w.
+#ifndef PF_FIX8_GLOBAL
+#define PF_FIX8_GLOBAL 0   // 1: the run lookup reads k_runs' table in global memory, not its LDS copy (SF1: no faster, §4.40)
+#endif
+__device__ __forceinline__ int flat_fixed8(FixedLds& S, const DevChunk& ck, [[maybe_unused]] const IdRunTab* T, int w_,
+                                           const uint8_t* ids, uint64_t ids_n_, int id_bw_, uint64_t slot_base, uint32_t e_begin,
+                                           uint32_t e_end) {
+    const uint32_t tid = threadIdx.x;
+    // the page's numbers are the same in every lane: kept in scalar registers (a section is under 4 GiB: body_len)
+    const int w = __builtin_amdgcn_readfirstlane(w_), id_bw = __builtin_amdgcn_readfirstlane(id_bw_);
+    const uint64_t ids_n = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(ids_n_))));
+    const uint32_t dn = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(ck.dict_n))));
+    const bool dlds = DICT_LDS > 0 && uint64_t(dn) * uint64_t(w) <= DICT_LDS;
+    const uint32_t mis = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(reinterpret_cast<uintptr_t>(ids) & 3u))));
+    const FixMemGlobal frame{(const PF_GLOBAL uint8_t*)(ids) - mis};
+    const uint32_t nr = uint32_t(S.nvrun);
+#if PF_FIX8_GLOBAL
+    const FixRowsRt rows{T->rows, nr, S.vcover};
+#else
+    const FixRowsLds rows{S.vrun};
+#endif
+    int bad = 0;
+    [[maybe_unused]] uint32_t nslow = 0;
+    for (uint32_t eb = e_begin; eb < e_end; eb += FIX_GR * 8u * NT) {
+        // ---- the run lookups and the id loads of this thread's groups, all issued before any is waited for
+        uint32_t q[FIX_GR][FIX_NDW];   // a group's id words (FIX_CONST: q[.][0] is the id)
+        uint32_t meta[FIX_GR];         // its kind << 8 | the bit of q[.][0] its first id starts at
+        #pragma unroll
+        for (uint32_t g = 0; g < FIX_GR; g++) {
+            #pragma unroll
+            for (int i = 0; i < FIX_NDW; i++) q[g][i] = 0;
+            meta[g] = FIX_SLOW << 8;
+            const uint32_t e0 = eb + 8u * (tid + NT * g);
+            if (e0 < e_end) {
+                const FixGrp G = fix_locate(rows, nr, e0, min(8u, e_end - e0), id_bw, mis, ids_n);
+                if (G.kind == FIX_CONST) q[g][0] = G.val;
+                else if (G.kind == FIX_PACKED) fix_load(id_bw, G.off4, frame, q[g]);
+                meta[g] = (G.kind << 8) | (G.kind == FIX_PACKED ? G.val : 0u);
+            }
+        }
+        // ---- the dictionary, behind the id loads and without waiting for them; the one barrier
+        if (eb == e_begin && dlds) {
+            if (w == 8) fixed8_stage_dict(S.dict, (const PF_GLOBAL uint64_t*)(ck.dict_data), dn);
+            else fixed8_stage_dict(reinterpret_cast<uint32_t*>(S.dict), (const PF_GLOBAL uint32_t*)(ck.dict_data), dn);
+            __syncthreads();
+        }
+        // ---- group by group: ids, gather, store. One text for the FIX_GR groups: the next group's words move down
+        #pragma unroll 1
+        for (uint32_t g = 0; g < FIX_GR; g++) {
+            const uint32_t e0 = eb + 8u * (tid + NT * g);
+            if (e0 < e_end) {
+                const uint32_t n = min(8u, e_end - e0), kind = meta[0] >> 8;
+                uint32_t id[8];
+                if (kind == FIX_PACKED) {
+                    fix_unpack(id_bw, q[0], meta[0] & 0xffu, id);
+                } else if (kind == FIX_CONST) {
+                    #pragma unroll
+                    for (uint32_t k = 0; k < 8; k++) id[k] = q[0][0];
+                } else {   // entry by entry, as flat_present_fixed
+                    nslow++;
+                    int r = run_find(S.vrun, S.nvrun, e0);
+                    #pragma unroll
+                    for (uint32_t k = 0; k < 8; k++) {
+                        id[k] = 0;
+                        if (k >= n) continue;
+                        const uint32_t e = e0 + k;
+                        while (e >= S.vrun[r].first + S.vrun[r].count) r++;
+                        const Run R = S.vrun[r];
+                        id[k] = R.data;
+                        if (R.packed) {
+                            const uint64_t bit = uint64_t(R.data) + uint64_t(e - R.first) * uint64_t(id_bw);
+                            id[k] = (bit >> 3) + 12 <= ids_n ? bits_fast(ids + (bit >> 3), uint32_t(bit & 7), id_bw)
+                                                             : fix_bits_pad(ids, ids_n, bit, id_bw);
+                        }
+                    }
+                }
+                #pragma unroll
+                for (uint32_t k = 0; k < 8; k++) {   // (entries past the block / bad ids load element 0)
+                    if (k < n && id[k] >= dn) bad = 1;
+                    id[k] = id[k] < dn ? id[k] : 0u;
+                }
+                if (w == 8)
+                    fixed8_gather_store<uint64_t>(dlds ? S.dict : nullptr, (const PF_GLOBAL uint64_t*)(ck.dict_data), id,
+                                                  (PF_GLOBAL uint64_t*)(ck.values) + slot_base + e0, n);
+                else
+                    fixed8_gather_store<uint32_t>(dlds ? reinterpret_cast<const uint32_t*>(S.dict) : nullptr,
+                                                  (const PF_GLOBAL uint32_t*)(ck.dict_data), id,
+                                                  (PF_GLOBAL uint32_t*)(ck.values) + slot_base + e0, n);
+            }
+            #pragma unroll
+            for (uint32_t h = 0; h + 1 < FIX_GR; h++) {
+                meta[h] = meta[h + 1];
+                #pragma unroll
+                for (int i = 0; i < FIX_NDW; i++) q[h][i] = q[h + 1][i];
+            }
+        }
+    }
+    // all present: the block's validity bits are ones
+    if (ck.max_def > 0 && ck.validity) fill_valid_ones(ck, slot_base + e_begin, slot_base + e_end);
+#ifdef PF_DIAG
+    if (nslow) FIX8_COUNT(1, nslow);
+    if (tid == 0) FIX8_COUNT(0, 1);
+#endif
+    return __syncthreads_or(bad) ? 1 : 0;
+}
+
 // k_flat for fixed-width pages whose levels are all present (the common case), with a small LDS
 // footprint and its own register budget: one workgroup per (page, FBLK block). Marks the page
 // done; k_flat decodes everything else (strings, pages with nulls).
 // Returns whether the block took its (page, block) (block-uniform); false: k_flat's body decodes it.
+// MODE: 0 = k_flat_all's copy (flat_present_fixed for every block, the text it has always had), 1 = k_flat_fixed (the
+// eight-a-thread body where it applies), 2 = the diagnostics build's k_flat_fixed under PF_FIX8=0 (as 0, counted).
+template <int MODE>
 __device__ __forceinline__ bool flat_fixed_block(FixedLds& S, const DevChunk* __restrict__ chunks, DevPage* pages, const int2 pbk,
                                  DevChunkResult* res) {
     if (pbk.x < 0) return true;   // padding of the XCD-grouped block list (runtime)
@@ -388,8 +618,25 @@ __device__ __forceinline__ bool flat_fixed_block(FixedLds& S, const DevChunk* __
     // values already in place: the executor decoded the page without falling back (a redo / serial
     // fallback writes the body to scratch instead, and the page is decoded from there)
     const bool direct = dval & (jf <= FB_WHOLE);
-    const int err = flat_present_fixed(S, ck, pg, s, dict, boolean, enc, w, ids, ids_n, id_bw,
-                                       uint64_t(pg.entry_start), e_begin, e_end, direct);
+    int err;
+    if constexpr (MODE == 1) {
+        // the eight-a-thread body: a dictionary page of 4- or 8-byte values with an aligned dictionary, a run table
+        // that covers the page, ids of at most FIX_BW_MAX bits. Everything else as before.
+        const bool fix8 = dict && tab && !direct && (w == 4 || w == 8) && ck.dict_data != nullptr && ck.dict_n > 0 &&
+                          (reinterpret_cast<uintptr_t>(ck.dict_data) & uintptr_t(w - 1)) == 0 && S.vres == 0 &&
+                          id_bw <= FIX_BW_MAX && s.val_n > 0;
+        if (fix8) {
+            err = flat_fixed8(S, ck, T, w, ids, ids_n, id_bw, uint64_t(pg.entry_start), e_begin, e_end);
+        } else {
+            if (dict && tid == 0) FIX8_COUNT(2, 1);
+            err = flat_present_fixed(S, ck, pg, s, dict, boolean, enc, w, ids, ids_n, id_bw,
+                                     uint64_t(pg.entry_start), e_begin, e_end, direct);
+        }
+    } else {
+        if constexpr (MODE == 2) { if (dict && tid == 0) FIX8_COUNT(2, 1); }
+        err = flat_present_fixed(S, ck, pg, s, dict, boolean, enc, w, ids, ids_n, id_bw,
+                                 uint64_t(pg.entry_start), e_begin, e_end, direct);
+    }
 #ifdef PF_STAMPS
     if (tid == 0) { const unsigned long long dt_ = __builtin_amdgcn_s_memtime() - ft0; PSTAMP(1, dt_); PSTAMP(0, 1); atomicMax(&pf_pstamps[9], dt_); }
 #endif
@@ -413,8 +660,16 @@ __global__ __launch_bounds__(NT, PF_FIXED_OCC) void k_flat_fixed(const DevChunk*
                                                               const int2* __restrict__ blocks, DevChunkResult* res, int* fbq) {
     __shared__ FixedLds S;
     const int2 pbk = blocks[blockIdx.x];
-    if (!flat_fixed_block(S, chunks, pages, pbk, res)) null_fallback(fbq, pbk);
+    if (!flat_fixed_block<1>(S, chunks, pages, pbk, res)) null_fallback(fbq, pbk);
 }
+#ifdef PF_DIAG   // PF_FIX8=0 (diagnostics build): flat_present_fixed for every block, as before the eight-a-thread body
+__global__ __launch_bounds__(NT, PF_FIXED_OCC) void k_flat_fixed_old(const DevChunk* __restrict__ chunks, DevPage* pages,
+                                                                  const int2* __restrict__ blocks, DevChunkResult* res, int* fbq) {
+    __shared__ FixedLds S;
+    const int2 pbk = blocks[blockIdx.x];
+    if (!flat_fixed_block<2>(S, chunks, pages, pbk, res)) null_fallback(fbq, pbk);
+}
+#endif
 
 // One workgroup per (page, FBLK block of entries). Pages whose levels are all present (max_def
 // == 0 or RLE runs of max_def) are decoded block by block in parallel: value index = entry
@@ -756,7 +1011,7 @@ __global__ __launch_bounds__(NT, PF_FLAT_OCC) void k_flat_all(const DevChunk* __
         const int nq = fbq[0], g = int(gridDim.x) - n;
         for (int i = int(blockIdx.x) - n; i < nq; i += g) {
             const int2 pq = reinterpret_cast<const int2*>(fbq + 4)[i];
-            if (!flat_fixed_block(S.f, chunks, pages, pq, res)) {
+            if (!flat_fixed_block<0>(S.f, chunks, pages, pq, res)) {
                 __syncthreads();
                 flat_block(S.g, chunks, pages, pq, res);
             }
@@ -765,7 +1020,7 @@ __global__ __launch_bounds__(NT, PF_FLAT_OCC) void k_flat_all(const DevChunk* __
         return;
     }
     const int2 pbk = blocks[blockIdx.x];
-    if (flat_fixed_block(S.f, chunks, pages, pbk, res)) return;
+    if (flat_fixed_block<0>(S.f, chunks, pages, pbk, res)) return;
     __syncthreads();   // the fixed body's LDS reads are done before the general body reuses it
     flat_block(S.g, chunks, pages, pbk, res);
 }
@@ -782,6 +1037,14 @@ void launch_flat(const DevChunk* d_chunks, DevPage* d_pages, const int* d_list, 
     // fourth through the launchers of the units that define them.
     const int2* blocks = reinterpret_cast<const int2*>(d_list);
     launch_flat_null(d_chunks, d_pages, blocks + nfix + n, n4, n8, d_fbq, d_res, st, nc, stagger);
+#ifdef PF_DIAG
+    // PF_FIX8=0: k_flat_fixed without the eight-a-thread body. Read here and not with the other PfOpts switches at
+    // pf_ctx_create, because this launcher's signature is the runtime's; the product library has no such read.
+    const char* fix8_env = std::getenv("PF_FIX8");
+    if (nfix > 0 && fix8_env && fix8_env[0] == '0')
+        hipLaunchKernelGGL(k_flat_fixed_old, dim3(nfix), dim3(NT), 0, st, d_chunks, d_pages, blocks, d_res, d_fbq);
+    else
+#endif
     if (nfix > 0) hipLaunchKernelGGL(k_flat_fixed, dim3(nfix), dim3(NT), 0, st, d_chunks, d_pages, blocks, d_res, d_fbq);
     // d_dblk: k_count_dict's (page, block) pairs, the blocks of flat dictionary BYTE_ARRAY pages: k_flat_dstr takes
     // the pages with a small dictionary of short values, k_flat_all's blocks of those then return at once
